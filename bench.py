@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: env steps/sec of the whole PPO loop (rollout + GAE + update, the
 `charts/SPS` definition of the reference, train.py:174,292) on big_track.json, "16 rays" (17 actual).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|cfg1|cfg2|cfg4|cfg4i]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|cfg1|cfg2|cfg4|cfg4i] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -118,6 +118,8 @@ def parse_args():
                     "or the library's one-shot all-reduce over peer-mapped buffers (pc_xchg_*)")
     ap.add_argument("--capture-collectives", action="store_true", help="multi-rank, backend nccl or --exchange p2p: capture the per-minibatch all-reduce into the epoch's update graph "
                     "(off by default: the minibatch steps are enqueued eagerly around an eager all-reduce)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed epochs, write what the last one computed (rank 0) "
+                    "as DIR/<name>.npy: see dump_outputs()")
     return ap.parse_args()
 
 
@@ -286,6 +288,33 @@ def cpu_baseline(cfg, torch, budget_s=5.0):
             "reference_python": {"value": py, "unit": "env steps/s", "cores": 1,
                                  "source": "BASELINE.md section 2: the reference's Python CarEnv on one Xeon 2.1 GHz core of the survey "
                                            "container (env only, big_track); it cannot travel to the GPU box, so it is quoted, not re-timed"}}
+
+
+DUMP_SAMPLE_ENVS = 256                 # --dump-outputs: env columns of the rollout buffers written (a fixed, seeded sample) ...
+DUMP_SAMPLE_BYTES = 60 << 20           # ... fewer when T x obs_dim would take the sample past this (the whole dump stays under 64 MB)
+
+
+def dump_outputs(tr, cfg, out_dir, torch, np):
+    """--dump-outputs: what the LAST timed epoch left its caller, as float32 .npy files -- the updated parameters (the flat buffer the
+    agent's tensors are views of), the four losses run_epoch reports (policy, value, entropy, total: metrics / train_iters), and the
+    rollout buffers, advantages, returns and next observation / flags for a fixed, seeded sample of envs (`env_index`, float64).
+    Inputs are seeded (PPOConfig.seed = 0), so two builds run with the same arguments can be compared array for array."""
+    torch.cuda.synchronize()
+    b = tr.buffer
+    T, N, D = b.obs_buf.shape
+    per_env = 4 * (T * (D + 8) + D + 2)
+    k = max(1, min(N, DUMP_SAMPLE_ENVS, DUMP_SAMPLE_BYTES // per_env))
+    sel = np.sort(np.random.default_rng(0).choice(N, size=k, replace=False))
+    idx = torch.as_tensor(sel, device=b.obs_buf.device)
+    out = {"params": tr.learner.flat_param, "losses": tr.learner.metrics / cfg.train_iters,
+           "obs": b.obs_buf[:, idx], "actions": b.act_buf[:, idx], "rewards": b.rew_buf[:, idx], "values": b.val_buf[:, idx],
+           "terminated": b.term_buf[:, idx], "truncated": b.trunc_buf[:, idx], "logprobs": b.logprob_buf[:, idx],
+           "advantages": b.adv_buf[:, idx], "returns": b.ret_buf[:, idx],
+           "next_obs": tr.next_obs[idx], "next_terminated": tr.next_term[idx], "next_truncated": tr.next_trunc[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "env_index.npy"), sel.astype(np.float64))
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def parity_check(tr, cfg, torch, np, envs=1024, steps=64):
@@ -605,6 +634,8 @@ def main():
     if tr.learner.collective and not tr.learner._can_capture_update():
         tr.learner.exchange_events = []      # HIP events around every eagerly enqueued exchange of the timed epochs (a captured one cannot be bracketed)
     dt = timed(tr, args.steps)
+    if args.dump_outputs and rank == 0:  # before anything below runs the trainer's buffers again (the GAE leg rewrites adv / ret)
+        dump_outputs(tr, cfg, args.dump_outputs, torch, np)
     try:                                 # the stand-alone env-step probe, outside the timed region (it is not part of the path)
         probe_res = run_probe()
     except Exception as ex:              # (the probe must never take the benchmark line down with it)

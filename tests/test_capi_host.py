@@ -240,6 +240,36 @@ def test_bench_algorithmic_counts_are_surveys_figures_for_every_ray_count_and_tr
     assert 1 <= usable <= host and (quota is None or quota > 0)
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_under_64_mb(tmp_path, monkeypatch):
+    """bench.py's dump_outputs() on host buffers: every array float32 / float64, the env sample seeded (the same columns from call to
+    call) and cut so that the dump stays under 64 MB however long the rollout; the sampled columns are the buffer's own."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    for T, N, D, k in ((1024, 4096, 23, 256), (20000, 300, 23, 25), (8, 100, 39, 100)):     # (T = 20000: 2.5 MB per env column)
+        buf = pc.Buffer((D,), T, N, torch.device("cpu"))
+        buf.obs_buf.normal_()
+        buf.adv_buf, buf.ret_buf = torch.randn(T, N), torch.randn(T, N)
+        tr = types.SimpleNamespace(buffer=buf, learner=types.SimpleNamespace(flat_param=torch.randn(14858), metrics=torch.randn(4)),
+                                   next_obs=torch.randn(N, D), next_term=torch.zeros(N), next_trunc=torch.zeros(N))
+        got = []
+        for rep in range(2):
+            out = tmp_path / f"{T}_{rep}"
+            b.dump_outputs(tr, types.SimpleNamespace(train_iters=40), str(out), torch, np)
+            files = sorted(os.listdir(out))
+            assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20, (T, N, D)
+            arrs = {f: np.load(out / f) for f in files}
+            assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+            got.append(arrs["env_index.npy"])
+        sel = got[0].astype(np.int64)
+        assert np.array_equal(got[0], got[1]) and len(np.unique(sel)) == len(sel) == k
+        assert np.array_equal(arrs["obs.npy"], buf.obs_buf[:, sel].numpy()) and np.array_equal(arrs["returns.npy"], buf.ret_buf[:, sel].numpy())
+        assert np.allclose(arrs["losses.npy"], (tr.learner.metrics / 40).numpy())
+
+
 def test_bench_main_never_reads_a_name_after_deleting_it_or_shadows_a_module_function():
     """bench.py's main() is 400 lines that only run end to end on a GPU box: two slips of the kind a CPU suite can still catch --
     a local read after its `del` (the trainer is deleted before the side measurements), a local that shadows a module-level

@@ -423,3 +423,36 @@ def test_bench_default_line_carries_every_baseline_config_and_the_exact_dtype():
     assert d["strict_fp32_value"]["value"] > 0 and d["fp32_grade_bf16x3_value"]["value"] > 0
     sf = d["strict_f64_fp32_value"]      # float64 env + exact fp32 policy chain: one persistent launch as well
     assert sf["dtype"] == "f64" and sf["rollout"] == "mega" and sf["kernel"] == "K9-literal" and sf["value"] > 5e8, sf
+
+
+def test_bench_dump_outputs_are_the_last_timed_epoch_and_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed epoch computed: float32 / float64 .npy files, under 64 MB, the env sample
+    the same from run to run.  Two runs with the same arguments write the same arrays bit for bit (seeded inputs, deterministic kernels);
+    one more timed step (--steps 3) is one more epoch: the JSON line says so and the parameters, losses and rollout move on."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(tag, steps):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--n-envs", "1024", "--n-steps", "64",
+                            "--steps", str(steps), "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip())
+        assert line["steps"] == steps and line["config"]["rollout"] == "mega"
+        names = sorted(os.listdir(out))
+        assert sum(os.path.getsize(out / f) for f in names) <= 64 << 20
+        return {f[:-4]: np.load(out / f) for f in names}
+
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    assert set(a) == {"params", "losses", "env_index", "obs", "actions", "rewards", "values", "terminated", "truncated", "logprobs",
+                      "advantages", "returns", "next_obs", "next_terminated", "next_truncated"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    k = len(a["env_index"])
+    assert a["obs"].shape == (64, k, 23) and a["rewards"].shape == a["advantages"].shape == (64, k) and a["next_obs"].shape == (k, 23)
+    assert a["params"].size == 14858 and a["losses"].shape == (4,) and np.isfinite(a["losses"]).all()
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert np.array_equal(a["env_index"], c["env_index"])
+    assert not np.array_equal(a["params"], c["params"]) and not np.array_equal(a["obs"], c["obs"])
