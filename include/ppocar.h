@@ -176,6 +176,28 @@ int pc_gae(int device, const float* rew, const float* val, const float* term, co
            const float* last_val, const float* last_term, const float* last_trunc, double gamma, double lam,
            int64_t T, int64_t N, float* adv, float* ret, void* stream);
 
+/* ---- episode statistics (gymnasium's RecordEpisodeStatistics: return and length, plus gates and laps decoded from each step's
+ * reward k = rint(r / reward_scale): a gate iff k in {1, 11, -2, 8}, a lap iff k in {11, 8}).  Per env, float64, all device:
+ *   carry [4][N] (in / out): return (scaled), length, gates, laps of the episode in progress.  Length 0 = a fresh episode;
+ *                -1 = its start was not observed: the episode that closes from there is dropped and the carry restarts at 0.
+ *   out   [7][N] (ACCUMULATED: the caller initialises 0, 0, 0, 0, 0, +inf, -inf): finished episodes, the sum of their scaled
+ *                returns, lengths, gates, laps; min and max scaled return.  Counts are exact float64 integers; the sums are exact
+ *                (every reward is an integer multiple of ulp(float(0.01 * reward_scale)); see kernels/gae_sample.hpp) while a
+ *                per-env sum stays below 2^53 of those units.
+ * pc_episode_stats: rew, term, trunc [T][N] float32 in one of two layouts:
+ *   PC_EPISODE_BUFFER  the rollout buffer's: step t's flags in row t + 1, step T - 1's in last_term / last_trunc [N]; row 0 is not read
+ *   PC_EPISODE_STEPS   pc_env_step / pc_env_step_many rows: flags[t] belong to rew[t]; last_term / last_trunc are not read (may be NULL)
+ * pc_gae_episodes: pc_gae (same arguments, same adv / ret bits) with the statistics of the Buffer layout taken on the same loads.
+ * reward_scale must be finite and > 0 (else PC_ERR_INVALID_ARG). */
+#define PC_EPISODE_BUFFER 0
+#define PC_EPISODE_STEPS 1
+int pc_episode_stats(int device, const float* rew, const float* term, const float* trunc, const float* last_term,
+                     const float* last_trunc, int64_t T, int64_t N, int layout, double reward_scale, double* carry, double* out,
+                     void* stream);
+int pc_gae_episodes(int device, const float* rew, const float* val, const float* term, const float* trunc,
+                    const float* last_val, const float* last_term, const float* last_trunc, double gamma, double lam,
+                    int64_t T, int64_t N, float* adv, float* ret, double reward_scale, double* carry, double* out, void* stream);
+
 /* ---- Agent.get_action_and_value's sampling tail (model.py:35-40): for logits [N][A] float32
  * draw action ~ Categorical(logits) and return log_prob(action) and (optionally) the entropy.
  * Counter-based RNG (Philox-4x32-10) keyed by (seed, offset): the same (seed, offset, N, A)

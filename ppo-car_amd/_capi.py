@@ -16,6 +16,7 @@ PC_OK = 0
 PC_ERR_INVALID_ARG, PC_ERR_IO, PC_ERR_PARSE, PC_ERR_HIP, PC_ERR_UNSUPPORTED, PC_ERR_NO_DEVICE, PC_ERR_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 PC_XCHG_HANDLE_BYTES = 128
 PC_DTYPE_F32, PC_DTYPE_F64 = 0, 1
+PC_EPISODE_BUFFER, PC_EPISODE_STEPS = 0, 1
 PC_OPT_ROLLOUT_FORM, PC_OPT_ROLLOUT_EPW, PC_OPT_ROLLOUT_FAST = 1, 2, 3
 PC_KERNEL_NAMES = {0: "none", 1: "K9", 2: "K9s", 3: "K9-literal", 4: "K9d-filter", 5: "K9s-literal", 6: "K9d-selector", 7: "K9m", 8: "K9m-literal"}     # pc_env_last_rollout_kernel
 PC_STEP_NAMES = {0: "none", 1: "K1", 2: "K1f", 3: "K1f-table"}     # pc_env_last_step_kernel
@@ -78,6 +79,8 @@ _sig = {
     "pc_env_get_state": (_i, [_vp] * 9),
     "pc_env_set_state": (_i, [_vp] * 9),
     "pc_gae": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _vp]),
+    "pc_episode_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp, _vp]),
+    "pc_gae_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_sample": (_i, [_i, _vp, _i64, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
     "pc_policy_create": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pc_policy_destroy": (None, [_vp]),

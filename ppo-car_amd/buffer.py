@@ -39,8 +39,10 @@ class Buffer:
         return (self.obs_buf[t], self.act_buf[t], self.rew_buf[t], self.val_buf[t], self.term_buf[t], self.trunc_buf[t],
                 self.logprob_buf[t])
 
-    def calculate_advantages(self, last_vals, last_terminateds, last_truncateds):
-        """buffer.py:36-64: GAE(lambda) with separate terminated / truncated masks -> (adv_buf, ret_buf)."""
+    def calculate_advantages(self, last_vals, last_terminateds, last_truncateds, episodes=None):
+        """buffer.py:36-64: GAE(lambda) with separate terminated / truncated masks -> (adv_buf, ret_buf).
+        episodes: an EpisodeStats (ppo-car_amd/episodes.py) -- its carry and out are updated from the same rows by the same
+        launch (pc_gae_episodes: the same adv / ret bits as pc_gae)."""
         assert self.ptr == self.capacity, "Buffer not full"
         if self.device.type != "cuda":
             raise RuntimeError("Buffer.calculate_advantages runs the HIP GAE kernel: the buffer must live on the GPU")
@@ -53,6 +55,14 @@ class Buffer:
             self.ret_buf = torch.empty_like(self.rew_buf)
         adv, ret = self.adv_buf, self.ret_buf
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if episodes is not None:
+            assert episodes.num_envs == N and episodes.device == torch.device("cuda", dev)
+            check(lib.pc_gae_episodes(dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(),
+                                      self.trunc_buf.data_ptr(), lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), float(self.gamma),
+                                      float(self.gae_lambda), T, N, adv.data_ptr(), ret.data_ptr(), episodes.reward_scaling,
+                                      episodes.carry.data_ptr(), episodes.out.data_ptr(), stream), "pc_gae_episodes")
+            return adv, ret
         check(lib.pc_gae(self.device.index if self.device.index is not None else torch.cuda.current_device(),
                          self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(), self.trunc_buf.data_ptr(),
                          lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), float(self.gamma), float(self.gae_lambda), T, N,

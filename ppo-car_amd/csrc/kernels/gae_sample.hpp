@@ -70,6 +70,206 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ rew,
 }
 
 // ------------------------------------------------------------------------------------------
+// K3e: episode statistics (gymnasium's RecordEpisodeStatistics, plus gates and laps) from the rows K3 streams.
+// One lane per env, serial in t, REVERSE like K3: a boundary after step t (its terminated or truncated flag) closes the
+// segment to its right; the right-most closed segment is the new carry, every other one a finished episode; the left-most
+// segment adds the carry-in (the episode in progress when the window began) and finishes at the first boundary.
+//   Decoding: the reward is (float)(rw * s) with rw a sum of the reference's constants (car_env.py:700-748: 0.01 forward,
+//   +1 gate, +10 lap, -3 crash), so k = rint(r / s) is one of {0, 1, 11, -3, -2, 8} with a margin >= 0.49:
+//   a gate iff k in {1, 11, -2, 8}, a lap iff k in {11, 8}.
+//   Exactness: every float32 reward is an integer multiple of u = ulp(f32(0.01 s)) (no reward is smaller in magnitude
+//   and not zero).  An episode is at most 1000 steps (car_env.py:749), so every partial sum of one episode -- and of a
+//   window of T <= 1024 steps plus its carry -- stays below ~2000 * 11.01 / 0.01 * 2^24 u < 2^45 u < 2^53 u: the float64
+//   sums are EXACT, in any order.  The reverse scan here and a forward numpy sum give the same bits.
+// Outputs (float64, structure of arrays, ACCUMULATED into what the caller initialised):
+//   out[0..6][N]: finished episodes, sum of their scaled returns, of their lengths, gates, laps; min / max scaled return
+//   carry[0..3][N] (in / out): return, length, gates, laps of the episode in progress; length -1 = start not observed
+//   (the episode that closes from there is dropped, and the carry restarts at 0).
+// ------------------------------------------------------------------------------------------
+struct EpisodeAcc {
+    double seg_ret = 0.0;               // the open segment: from the scan position to the nearest boundary on its right
+    int seg_len = 0, seg_g = 0, seg_l = 0;
+    bool closed = false;                // a boundary has been met: the right-most segment is already the carry-out
+    double c_ret = 0.0;                 // carry-out (valid once closed)
+    int c_len = 0, c_g = 0, c_l = 0;
+    int n = 0, s_len = 0, s_g = 0, s_l = 0;   // finished episodes
+    double s_ret = 0.0, mn = INFINITY, mx = -INFINITY;
+
+    // step t of the reverse scan; `done`: step t ended an episode (the boundary after it)
+    __device__ __forceinline__ void step(const float r, const bool done, const double inv_s) {
+        const bool fin = done & closed, first = done & !closed;
+        n += fin;
+        s_ret += fin ? seg_ret : 0.0;
+        s_len += fin ? seg_len : 0;
+        s_g += fin ? seg_g : 0;
+        s_l += fin ? seg_l : 0;
+        mn = fin ? fmin(mn, seg_ret) : mn;
+        mx = fin ? fmax(mx, seg_ret) : mx;
+        c_ret = first ? seg_ret : c_ret;
+        c_len = first ? seg_len : c_len;
+        c_g = first ? seg_g : c_g;
+        c_l = first ? seg_l : c_l;
+        closed |= done;
+        const int k = (int)rint((double)r * inv_s);
+        seg_ret = (done ? 0.0 : seg_ret) + (double)r;    // the float64 chain: independent of K3's float32 recurrence
+        seg_len = (done ? 0 : seg_len) + 1;
+        seg_g = (done ? 0 : seg_g) + ((k == 1) | (k == 11) | (k == -2) | (k == 8));
+        seg_l = (done ? 0 : seg_l) + ((k == 11) | (k == 8));
+    }
+
+    // the left-most segment meets the carry-in; carry and out are read once and written once
+    __device__ __forceinline__ void finish(double* __restrict__ carry, double* __restrict__ out, const int64_t e, const int64_t N) {
+        const double cin_len = carry[N + e];
+        const bool seen = cin_len >= 0.0;
+        if (seen) {
+            seg_ret = carry[e] + seg_ret;
+            seg_len += (int)cin_len;
+            seg_g += (int)carry[2 * N + e];
+            seg_l += (int)carry[3 * N + e];
+        }
+        if (closed) {
+            if (seen) {
+                n += 1;
+                s_ret += seg_ret;
+                s_len += seg_len;
+                s_g += seg_g;
+                s_l += seg_l;
+                mn = fmin(mn, seg_ret);
+                mx = fmax(mx, seg_ret);
+            }
+        } else {            // no boundary in the window: the carry goes on (a sentinel stays one)
+            c_ret = seen ? seg_ret : 0.0;
+            c_len = seen ? seg_len : -1;
+            c_g = seen ? seg_g : 0;
+            c_l = seen ? seg_l : 0;
+        }
+        carry[e] = c_ret;
+        carry[N + e] = (double)c_len;
+        carry[2 * N + e] = (double)c_g;
+        carry[3 * N + e] = (double)c_l;
+        out[e] += (double)n;
+        out[N + e] += s_ret;
+        out[2 * N + e] += (double)s_len;
+        out[3 * N + e] += (double)s_g;
+        out[4 * N + e] += (double)s_l;
+        out[5 * N + e] = fmin(out[5 * N + e], mn);
+        out[6 * N + e] = fmax(out[6 * N + e], mx);
+    }
+};
+
+// K3e fused: K3's recurrence (the same float32 operations in the same order: adv / ret bit-identical to gae_kernel) plus
+// EpisodeAcc on the rows already in registers -- no added HBM traffic per transition.
+__global__ __launch_bounds__(256) void gae_episode_kernel(const float* __restrict__ rew, const float* __restrict__ val,
+                                                          const float* __restrict__ term, const float* __restrict__ trunc,
+                                                          const float* __restrict__ last_val, const float* __restrict__ last_term,
+                                                          const float* __restrict__ last_trunc, const float g, const float gl,
+                                                          const int64_t T, const int64_t N, float* __restrict__ adv,
+                                                          float* __restrict__ ret, const double inv_s, double* __restrict__ carry,
+                                                          double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    float next_val = last_val[e];
+    const float lt = last_term[e], ltr = last_trunc[e];
+    float tmask = 1.0f - lt;
+    float trmask = 1.0f - ltr;
+    bool done = (lt != 0.0f) | (ltr != 0.0f);
+    float last_gae = 0.0f;
+    EpisodeAcc acc;
+    constexpr int U = 8;
+    int64_t t = T - 1;
+    for (; t >= U - 1; t -= U) {
+        float r[U], v[U], tm[U], tr[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int64_t off = (t - j) * N + e;
+            r[j] = rew[off];
+            v[j] = val[off];
+            tm[j] = term[off];
+            tr[j] = trunc[off];
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int64_t off = (t - j) * N + e;
+            float tmp = g * next_val;
+            tmp = tmp * tmask;
+            float delta = r[j] + tmp;
+            delta = delta - v[j];
+            float c = gl * tmask;
+            c = c * trmask;
+            c = c * last_gae;
+            last_gae = delta + c;
+            adv[off] = last_gae;
+            ret[off] = last_gae + v[j];
+            acc.step(r[j], done, inv_s);
+            next_val = v[j];
+            tmask = 1.0f - tm[j];
+            trmask = 1.0f - tr[j];
+            done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
+        }
+    }
+    for (; t >= 0; --t) {
+        const int64_t off = t * N + e;
+        const float r = rew[off], v = val[off];
+        float tmp = g * next_val;
+        tmp = tmp * tmask;
+        float delta = r + tmp;
+        delta = delta - v;
+        float c = gl * tmask;
+        c = c * trmask;
+        c = c * last_gae;
+        last_gae = delta + c;
+        adv[off] = last_gae;
+        ret[off] = last_gae + v;
+        acc.step(r, done, inv_s);
+        next_val = v;
+        const float tmf = term[off], trf = trunc[off];
+        tmask = 1.0f - tmf;
+        trmask = 1.0f - trf;
+        done = (tmf != 0.0f) | (trf != 0.0f);
+    }
+    acc.finish(carry, out, e, N);
+}
+
+// K3e standalone: the same accounting without GAE.  STEPS = false: the Buffer layout (step t's flags in row t + 1, step
+// T - 1's in last_*; row 0 is never read); STEPS = true: flags[t] belong to rew[t] (pc_env_step / pc_env_step_many rows).
+template <bool STEPS>
+__global__ __launch_bounds__(256) void episode_kernel(const float* __restrict__ rew, const float* __restrict__ term,
+                                                      const float* __restrict__ trunc, const float* __restrict__ last_term,
+                                                      const float* __restrict__ last_trunc, const int64_t T, const int64_t N,
+                                                      const double inv_s, double* __restrict__ carry, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    bool done = STEPS ? false : (last_term[e] != 0.0f) | (last_trunc[e] != 0.0f);
+    EpisodeAcc acc;
+    constexpr int U = 8;
+    int64_t t = T - 1;
+    for (; t >= U - 1; t -= U) {
+        float r[U], tm[U], tr[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int64_t off = (t - j) * N + e;
+            r[j] = rew[off];
+            tm[j] = term[off];
+            tr[j] = trunc[off];
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (STEPS) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
+            acc.step(r[j], done, inv_s);
+            if (!STEPS) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
+        }
+    }
+    for (; t >= 0; --t) {
+        const int64_t off = t * N + e;
+        const float r = rew[off];
+        if (STEPS) done = (term[off] != 0.0f) | (trunc[off] != 0.0f);
+        acc.step(r, done, inv_s);
+        if (!STEPS && t > 0) done = (term[off] != 0.0f) | (trunc[off] != 0.0f);
+    }
+    acc.finish(carry, out, e, N);
+}
+
+// ------------------------------------------------------------------------------------------
 // K4: categorical sample / log_prob / entropy (model.py:35-40), Philox-4x32-10 counter RNG
 // ------------------------------------------------------------------------------------------
 // exp(x) for the rollout-time softmax, x = logit - max <= 0: v_exp_f32(x * log2(e)), two instructions.  expf() spends eight

@@ -9,6 +9,8 @@
 //   K2  env_reset_kernel<T>             CarEnv.reset for every env (car_env.py:605-691); reset_obs_kernel<T> computes
 //                                       each track's constant reset observation once at create
 //   K3  gae_kernel                      Buffer.calculate_advantages (buffer.py:36-64)
+//   K3e gae_episode_kernel / episode_kernel<STEPS>   episode return, length, gates and laps on K3's rows (pc_gae_episodes) or alone
+//                                       (pc_episode_stats)
 //   K4  sample_kernel                   Categorical(logits).sample / log_prob / entropy (model.py:35-40)
 //   K5  policy_kernel<KS, SPLIT, PREC>  Agent.get_action_and_value(x) of the rollout (model.py:34-41): both MLPs on the
 //                                       matrix cores + the draw; policy_pack*_kernel build its LDS weight image
@@ -1082,6 +1084,47 @@ int pc_gae(int device, const float* rew, const float* val, const float* term, co
     // gamma and gamma*lambda are Python floats that torch casts to float32 at the multiply
     hipLaunchKernelGGL(gae_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val, last_term,
                        last_trunc, (float)gamma, (float)(gamma * lam), T, N, adv, ret);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_episode_stats(int device, const float* rew, const float* term, const float* trunc, const float* last_term,
+                     const float* last_trunc, int64_t T, int64_t N, int layout, double reward_scale, double* carry, double* out,
+                     void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!rew || !term || !trunc || !carry || !out || T < 1 || N < 1) return PC_ERR_INVALID_ARG;
+    if (layout != PC_EPISODE_BUFFER && layout != PC_EPISODE_STEPS) return PC_ERR_INVALID_ARG;
+    if (layout == PC_EPISODE_BUFFER && (!last_term || !last_trunc)) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale)) return PC_ERR_INVALID_ARG;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int blocks = (int)((N + 255) / 256);
+    if (layout == PC_EPISODE_STEPS)
+        hipLaunchKernelGGL(episode_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, term, trunc, last_term,
+                           last_trunc, T, N, 1.0 / reward_scale, carry, out);
+    else
+        hipLaunchKernelGGL(episode_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, term, trunc, last_term,
+                           last_trunc, T, N, 1.0 / reward_scale, carry, out);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_gae_episodes(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
+                    const float* last_term, const float* last_trunc, double gamma, double lam, int64_t T, int64_t N, float* adv,
+                    float* ret, double reward_scale, double* carry, double* out, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!rew || !val || !term || !trunc || !last_val || !last_term || !last_trunc || !adv || !ret || !carry || !out || T < 1 || N < 1)
+        return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale)) return PC_ERR_INVALID_ARG;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int blocks = (int)((N + 255) / 256);
+    hipLaunchKernelGGL(gae_episode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
+                       last_term, last_trunc, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0 / reward_scale, carry, out);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }

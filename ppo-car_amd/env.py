@@ -113,9 +113,12 @@ class VecCarEnv:
     `num_rays` is Car's nominal ray count (car_env.py:227); the observation has 6 + R entries with
     R = len(range(0, 360, 360 // num_rays)) exactly as the reference produces them.
     tracks: one path / Track, or a list of them with `track_id` [N] picking each env's track.
+    record_episode_statistics=True (gymnasium's RecordEpisodeStatistics, on the device): step() adds infos["episode"] = {"r" float64,
+    "l", "gates", "laps" int32} [N], valid where infos["_episode"]; step() and step_many() accumulate what episode_statistics() returns.
     """
 
-    def __init__(self, n_envs, tracks, num_rays=12, reward_scaling=1.0, device="cuda", dtype="f32", track_id=None):
+    def __init__(self, n_envs, tracks, num_rays=12, reward_scaling=1.0, device="cuda", dtype="f32", track_id=None,
+                 record_episode_statistics=False):
         self.device = torch.device("cuda", _device_index(device))
         self.num_envs = int(n_envs)
         self.num_rays = int(num_rays)
@@ -126,6 +129,11 @@ class VecCarEnv:
         self._track_id = None if track_id is None else np.ascontiguousarray(track_id, np.uint8)
         self._opts = {}
         self._build(tracks)
+        self._episodes = None
+        if record_episode_statistics:
+            from .episodes import EpisodeStats
+            self._episodes = EpisodeStats(self.num_envs, self.reward_scaling, self.device)
+            self._episode_step_out = self._episodes.new_out()
 
     # ---- construction ---------------------------------------------------------------------
     def _build(self, tracks):
@@ -190,6 +198,8 @@ class VecCarEnv:
         obs = out if out is not None else self._new(self.num_envs, self.obs_dim)
         check(lib.pc_env_reset(self._h, self._ptr(obs, torch.float32, self.num_envs * self.obs_dim, "obs"), self._stream()),
               "pc_env_reset")
+        if self._episodes is not None:
+            self._episodes.reset()
         return obs, {}
 
     def infos(self):
@@ -228,7 +238,33 @@ class VecCarEnv:
             infos["gates_passed"] = gates_passed
         if final_obs is not None:
             infos["final_observation"] = final_obs
+        if self._episodes is not None:
+            self._record_step(rew, term, trunc, infos)
         return obs, rew, term, trunc, infos
+
+    def _record_step(self, rew, term, trunc, infos):
+        """infos["episode"] / ["_episode"] of the episodes this step finished (gymnasium's vector format), and their totals into the
+        running statistics."""
+        ep, so = self._episodes, self._episode_step_out
+        ep.clear(so)
+        ep.update(rew, term, trunc, layout="steps", out=so)
+        acc = ep.out
+        acc[:5] += so[:5]
+        torch.minimum(acc[5], so[5], out=acc[5])
+        torch.maximum(acc[6], so[6], out=acc[6])
+        infos["episode"] = {"r": so[1] / self.reward_scaling, "l": so[2].to(torch.int32), "gates": so[3].to(torch.int32),
+                            "laps": so[4].to(torch.int32)}
+        infos["_episode"] = so[0] > 0
+
+    def episode_statistics(self):
+        """The statistics of the episodes finished since the last call (record_episode_statistics=True), as 0-d device tensors
+        (episodes; mean return (unscaled), return_min / _max, mean length, gates and laps per episode; NaN means when none finished),
+        then clears them.  No host synchronisation; episodes.to_host() turns them into floats / None."""
+        if self._episodes is None:
+            raise RuntimeError("VecCarEnv(record_episode_statistics=True) keeps episode statistics; this env does not")
+        s = self._episodes.summary()
+        self._episodes.clear()
+        return s
 
     def step_many(self, actions, out=None):
         """`for t in range(T): envs.step(actions[t])` as ONE call (pc_env_step_many): actions [T, N] int64 -> (obs [T, N, D], rewards,
@@ -248,6 +284,8 @@ class VecCarEnv:
                                    self._ptr(obs, torch.float32, T * N * D, "obs"), self._ptr(rew, torch.float32, T * N, "rewards"),
                                    self._ptr(term, torch.float32, T * N, "terminateds"), self._ptr(trunc, torch.float32, T * N, "truncateds"),
                                    self._stream()), "pc_env_step_many")
+        if self._episodes is not None:
+            self._episodes.update(rew, term, trunc, layout="steps")
         return obs, rew, term, trunc
 
     def last_step_kernel(self):
@@ -289,6 +327,8 @@ class VecCarEnv:
         if kw:
             raise TypeError(f"unknown state fields {sorted(kw)}")
         check(lib.pc_env_set_state(self._h, *[a.ctypes.data if a is not None else None for a in args]), "pc_env_set_state")
+        if self._episodes is not None:
+            self._episodes.forget()      # the injected episodes' history is unknown
 
     def launch_info(self):
         v = [C.c_int() for _ in range(4)]

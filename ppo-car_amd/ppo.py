@@ -25,6 +25,7 @@ from . import _capi
 from ._capi import check, lib
 from .buffer import Buffer
 from .env import VecCarEnv
+from .episodes import EpisodeStats, episode_scalars
 from .model import Agent
 
 
@@ -96,6 +97,8 @@ class PPOConfig:
     rollout_form: int = -1                 # pc_rollout's per-handle options (include/ppocar.h PC_OPT_ROLLOUT_*; every choice gives the
     rollout_epw: int = 0                   # same bits): form -1 automatic / 0 big / 1 small / 2, 3 without the LDS 1/den table; envs per
     rollout_fast: int = 1                  # workgroup 0 automatic / 16 / 32 / 128 / 256; fast 1 / 2 / 0 (table-driven modes on / generic sweep / off)
+    episode_stats: bool = False            # run_epoch adds charts/episodes, episodic_return (+ _min / _max), episodic_length, gates_per_episode,
+                                           # laps_per_episode: taken by the GAE launch on the rows it loads anyway (pc_gae_episodes)
 
 
 def flatten_parameters(module):
@@ -721,6 +724,7 @@ class Trainer:
         self._eager_rollouts = 0
         self.rollout_mode = None
         self.mega_events = None      # bench.py: list of (start, end) events around each pc_rollout launch
+        self.episodes = EpisodeStats(N, cfg.reward_scaling, self.device) if cfg.episode_stats else None   # carry 0: the envs were just reset
 
     # ---- train.py:173-195 ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -833,8 +837,10 @@ class Trainer:
             # train.py:200 -- the persistent rollout kernel has already evaluated the critic on the final observation
             in_kernel = self._aux_valid and self.cfg.bootstrap_value == "kernel"
             next_values = (self._boot_val if in_kernel else agent.get_value(self.next_obs)).reshape(1, -1)
+            if self.episodes is not None:
+                self.episodes.clear()       # this epoch's finished episodes only; the carry spans epochs
             adv, ret = buf.calculate_advantages(next_values, self.next_term.reshape(1, -1),
-                                                self.next_trunc.reshape(1, -1))                   # :203
+                                                self.next_trunc.reshape(1, -1), episodes=self.episodes)   # :203
         obs, act, _val, logprob = buf.get()                                                      # :206
         self.learner.update(obs.view(-1, *self.obs_dim), act.view(-1), logprob.view(-1), adv.view(-1), ret.view(-1))
         self._aux_valid = False     # the in-kernel bootstrap values belong to THAT rollout and THOSE parameters only
@@ -854,6 +860,7 @@ class Trainer:
         with torch.no_grad():   # train.py:272; the persistent rollout kernel delivers per-env totals (no second pass over rew_buf)
             rew_mean = (self._rew_sum.sum() / float(self.cfg.n_steps * self.cfg.n_envs)) if self._aux_valid else self.buffer.rew_buf.mean()
         self.update()
+        ep_tot = self.episodes.totals() if self.episodes is not None else None    # float64 [7], still on the device
         if ev:
             ev[2].record()
             self.phase_events.append(ev)
@@ -870,9 +877,13 @@ class Trainer:
                 dev = torch.cat([L.metrics / self.cfg.train_iters, rew_mean.reshape(1).to(torch.float32), lr, rng])
             host = torch.empty(7, dtype=torch.float32, pin_memory=True)
             host.copy_(dev, non_blocking=True)
+            host_ep = None
+            if ep_tot is not None:      # the episode totals in float64, next to the seven floats
+                host_ep = torch.empty(7, dtype=torch.float64, pin_memory=True)
+                host_ep.copy_(ep_tot, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            self._pending_scalars = (host, done, self.global_step_idx)
+            self._pending_scalars = (host, done, self.global_step_idx, host_ep)
             return prev
         self.flush_scalars()        # (a switch from lazy to synchronous calls drops nothing silently: the pending epoch is waited for)
         self.check_exchange()       # (synchronises; the scalars below are fetched anyway) a timed-out exchange stops the job HERE
@@ -886,27 +897,37 @@ class Trainer:
             dist.all_reduce(t)
             t /= self.world_size
             *m, avg_reward = t.tolist()
+            if ep_tot is not None:      # episodes of every rank: sums add, extremes by MIN / MAX
+                dist.all_reduce(ep_tot[:5], op=dist.ReduceOp.SUM)
+                dist.all_reduce(ep_tot[5:6], op=dist.ReduceOp.MIN)
+                dist.all_reduce(ep_tot[6:7], op=dist.ReduceOp.MAX)
         elapsed = time.time() - self.start_time
-        return {"losses/policy_loss": m[0], "losses/value_loss": m[1], "losses/entropy": m[2], "losses/total_loss": m[3],
-                "charts/avg_reward": avg_reward, "charts/learning_rate": self.learner.current_lr(),
-                "charts/SPS": self.global_step_idx / max(elapsed, 1e-9), "global_step": self.global_step_idx,
-                "elapsed": elapsed}
+        out = {"losses/policy_loss": m[0], "losses/value_loss": m[1], "losses/entropy": m[2], "losses/total_loss": m[3],
+               "charts/avg_reward": avg_reward, "charts/learning_rate": self.learner.current_lr(),
+               "charts/SPS": self.global_step_idx / max(elapsed, 1e-9), "global_step": self.global_step_idx,
+               "elapsed": elapsed}
+        if ep_tot is not None:
+            out.update(episode_scalars(ep_tot.tolist(), self.cfg.reward_scaling))
+        return out
 
     def flush_scalars(self):
         """The scalars of the last epoch run with sync="lazy" (waits for THAT epoch only), or None."""
         pend, self._pending_scalars = getattr(self, "_pending_scalars", None), None
         if pend is None:
             return None
-        host, done, gstep = pend
+        host, done, gstep, host_ep = pend
         done.synchronize()
         m = host.tolist()
         lr = m[5]
         if m[6] != 0.0 and self.device.type == "cuda":
             self.agent.check_policy_range(sync=True)    # weights outside the policy arithmetic's domain: precision 0 from the next rollout on (or PolicyRangeError)
         elapsed = time.time() - self.start_time
-        return {"losses/policy_loss": m[0], "losses/value_loss": m[1], "losses/entropy": m[2], "losses/total_loss": m[3],
-                "charts/avg_reward": m[4] / self.cfg.reward_scaling, "charts/learning_rate": lr,
-                "charts/SPS": gstep / max(elapsed, 1e-9), "global_step": gstep, "elapsed": elapsed}
+        out = {"losses/policy_loss": m[0], "losses/value_loss": m[1], "losses/entropy": m[2], "losses/total_loss": m[3],
+               "charts/avg_reward": m[4] / self.cfg.reward_scaling, "charts/learning_rate": lr,
+               "charts/SPS": gstep / max(elapsed, 1e-9), "global_step": gstep, "elapsed": elapsed}
+        if host_ep is not None:
+            out.update(episode_scalars(host_ep.tolist(), self.cfg.reward_scaling))
+        return out
 
     # ---- checkpoint / resume (SURVEY 8(f) row 1: the reference only saves agent.state_dict(), train.py:283,301) ----
     def state_dict(self):
@@ -918,7 +939,8 @@ class Trainer:
                 "next_obs": self.next_obs, "next_term": self.next_term, "next_trunc": self.next_trunc,
                 "rng_base": self.rng_base, "np_rng": L._np_rng.bit_generator.state, "epoch": self.epoch,
                 "global_step_idx": self.global_step_idx, "agent_rng_offset": self.agent._rng_offset,
-                "elapsed": time.time() - self.start_time, "config": dataclasses.asdict(self.cfg)}
+                "elapsed": time.time() - self.start_time, "config": dataclasses.asdict(self.cfg),
+                **({"episodes": self.episodes.state_dict()} if self.episodes is not None else {})}
 
     def load_state_dict(self, sd):
         L = self.learner
@@ -938,6 +960,8 @@ class Trainer:
             self.envs.set_state(**sd["env"])
             self.next_obs.copy_(sd["next_obs"]); self.next_term.copy_(sd["next_term"]); self.next_trunc.copy_(sd["next_trunc"])
             self.rng_base.copy_(sd["rng_base"])
+            if self.episodes is not None:       # a checkpoint without statistics: the episodes in progress have an unknown start
+                self.episodes.load_state_dict(sd["episodes"]) if "episodes" in sd else self.episodes.forget()
         L._np_rng.bit_generator.state = sd["np_rng"]
         L._opt_started = True
         self.epoch, self.global_step_idx = sd["epoch"], sd["global_step_idx"]

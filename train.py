@@ -53,6 +53,8 @@ def parse_args(argv=None):
     p.add_argument("--out-dir", default=".", help="where checkpoints/ and logs/ are created")
     p.add_argument("--lazy-logging", action="store_true", help="one rank: print and log one epoch behind the device (Trainer.run_epoch(sync=\"lazy\")) instead of "
                    "fetching every epoch's scalars before the next epoch is launched (the reference's order, the default: it costs ~1 %% at 65536 envs)")
+    p.add_argument("--episode-stats", action="store_true", help="print and log episodic return, length, gates and laps per episode "
+                   "(charts/episodes, charts/episodic_*, charts/gates_per_episode, charts/laps_per_episode)")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -94,7 +96,8 @@ def main(argv=None):
                     learning_rate_decay=args.learning_rate_decay, max_grad_norm=args.max_grad_norm,
                     reward_scaling=args.reward_scaling, track=args.track, num_rays=args.num_rays, env_dtype=args.env_dtype,
                     seed=args.seed, full_sweep=args.full_sweep, bootstrap_value=args.bootstrap_value,
-                    policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range)
+                    policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range,
+                    episode_stats=args.episode_stats)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
@@ -107,7 +110,12 @@ def main(argv=None):
     start = time.time()
     try:
         def report(ep, scalars):
-            print(f"Epoch {ep} done in {time.time() - start:.2f}s. Avg reward: {scalars['charts/avg_reward']:.4f}. ", flush=True)   # train.py:275-276
+            line = f"Epoch {ep} done in {time.time() - start:.2f}s. Avg reward: {scalars['charts/avg_reward']:.4f}. "   # train.py:275-276
+            if args.episode_stats:
+                ret = scalars["charts/episodic_return"]
+                line += (f"Episodes: {scalars['charts/episodes']}, return {ret:.3f}, length {scalars['charts/episodic_length']:.1f}, "
+                         f"laps {scalars['charts/laps_per_episode']:.3f}. " if ret is not None else "Episodes: 0. ")
+            print(line, flush=True)
             log.write(json.dumps(scalars) + "\n")
             log.flush()
         # --lazy-logging (one rank): the host runs one epoch AHEAD of what it prints (Trainer.run_epoch(sync="lazy")) -- the device never idles
