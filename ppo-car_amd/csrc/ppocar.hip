@@ -50,6 +50,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +58,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <unordered_set>
 #include <climits>
@@ -80,9 +82,12 @@
 // ------------------------------------------------------------------------------------------
 // Developer-only quick build (tools/ab_run.sh with -DPC_DEV_MIN=<mask>; never the product: the host layer refuses it like the
 // ablation build): the dispatch tables keep only the benchmarked kernels -- bit 0: rollout_kernel<6, 9, 2, 3> (target), bit 1:
-// rollout_small_kernel<6, 5, 2, 1, 16> (cfg1), bit 2: rollout_kernel<10, 17, 2, 1> (cfg2), bits 3 / 5: the literal form of bits 0 / 2
-// for F64 handles, bit 4: rollout_f64_kernel<6, 9, 2> (the filter form), bit 6: the literal form of bit 1; the fp16x2 policy kernels, the
-// float32 env-step kernels and the update kernels stay -- so that one kernel experiment compiles in seconds instead of 75.
+// rollout_small_kernel<6, 5, 2, 2, 16> (cfg1), bit 2: rollout_kernel<10, 17, 2, 1> (cfg2), bits 3 / 5: the literal form of bits 0 / 2
+// for F64 handles, bit 4: rollout_f64_kernel<6, 9, 2> (the filter form), bit 6: the literal form of bit 1, bit 7: the 16-envs-per-wave
+// form rollout_kernel<6, 5, 2, 3, false, 2> (big_track's layout), bit 8: its literal form; bits 0 / 3 also keep K1f's
+// env_steps_fast_kernel<9, 7, ...> for F32 / F64 handles.  The fp16x2 policy kernels, the float32 env-step kernels and the update
+// kernels stay -- so that one kernel experiment compiles in seconds instead of 75.  A plan whose instance the build left out is
+// PC_ERR_UNSUPPORTED.
 #ifdef PC_DEV_MIN
 #define PC_FULL(...) return PC_ERR_UNSUPPORTED
 #define PC_DEV(bit, ...) do { if constexpr (((PC_DEV_MIN) >> (bit)) & 1) { __VA_ARGS__; } else return PC_ERR_UNSUPPORTED; } while (0)
@@ -116,6 +121,21 @@ struct DeviceGuard {  // set the handle's device for the call, restore the calle
     }
     int dev_;
 };
+
+// Launch a 512-thread kernel with `lds` bytes of dynamic LDS.  Its limit is raised to 160 KB once per (kernel, device), not on every
+// call (pc_env_step is on the per-step path); device ids from 64 on have no bit in the set and raise it on every call.
+template <auto K, typename... Args>
+int launch_lds(int device, int blocks, size_t lds, hipStream_t st, Args... args) {
+    static std::atomic<uint64_t> raised{0};     // bit d: done for device d
+    const uint64_t bit = device < 64 ? 1ull << device : 0;
+    if (!(raised.load(std::memory_order_acquire) & bit)) {
+        HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        raised.fetch_or(bit, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(512), lds, st, args...);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
 
 constexpr int kMenu[] = {1, 2, 3, 5, 6, 9, 12, 17, 33};  // rays-per-lane instantiations of K1
 
@@ -153,6 +173,16 @@ struct pc_env {
     int lanes_override = 0;
     int lg = 0, rpl = 1, blocks = 0;
     std::vector<TrackHdr> hdr_host;
+    // what dispatch needs to know of the batch's tracks, fixed once env_create_impl has built them.  The two layouts are the tracks'
+    // own: PC_OPT_ROLLOUT_FAST's nv28 switch (it can change after create) applies at dispatch.
+    struct TrackFacts {
+        int max_G = 0, max_nV = 0, sum_nV = 0;   // reward gates, chain vertices: of the largest track; chain vertices of all tracks together
+        bool tabs = true;    // every track has its gather tables (F64 handles: and the selector inside its limits and the rotation table)
+        bool rden = true;    // ... its 1/den table
+        bool sel = true;     // ... the selector inside its limits
+        bool nv28 = true;    // ... big_track's layout: two loops of 12 walls, a padded chain of 28 vertices
+        bool loops = true;   // ... two equal loops of 13 or of 9 chain vertices (big_track.json, track.json: 8 walls per loop)
+    } facts;
     // device buffers
     double4* pv = nullptr;
     int4* iv = nullptr;
@@ -255,6 +285,16 @@ static void launch_step(const pc_env* e, const int64_t* actions, double reward_s
                            reward_scale, obs, reward, term, trunc, gates_passed, final_obs);
 }
 
+// env_steps_fast_kernel's arguments, handed by steps_fast_launch to the instance it picks (`tab`: the TAB instance)
+using StepsFastArgs = std::tuple<EnvParams<float>, const int64_t*, int, double, float*, float*, float*, float*, int, int, int32_t*, float*, int>;
+template <int RPL, int SWP, bool LIT, bool TWO = false>
+static int run_steps_fast(bool tab, int device, int blocks, size_t lds, hipStream_t st, const StepsFastArgs& args) {
+    return std::apply([&](auto... a) {
+        return tab ? launch_lds<env_steps_fast_kernel<RPL, SWP, true, LIT, TWO>>(device, blocks, lds, st, a...)
+                   : launch_lds<env_steps_fast_kernel<RPL, SWP, false, LIT, TWO>>(device, blocks, lds, st, a...);
+    }, args);
+}
+
 // K1f (env_steps_fast_kernel): T successive steps as one launch, where the shape has the table-driven form -- 12 / 16 / 32 nominal rays,
 // every track's gather tables inside the LDS limits, a mixed batch in blocks of one track per workgroup; F64 handles: every track inside
 // the selector's limits with its rotation table, every env's rotation on it (the conditions of pc_rollout's literal kernels).
@@ -262,64 +302,34 @@ static void launch_step(const pc_env* e, const int64_t* actions, double reward_s
 static int steps_fast_launch(pc_env* e, const int64_t* actions, int64_t T, double reward_scale, float* obs, float* reward, float* term,
                              float* trunc, bool table, hipStream_t st, int32_t* gates_passed = nullptr, float* final_obs = nullptr) {
     const bool f64 = e->dtype == PC_DTYPE_F64;
+    const pc_env::TrackFacts& f = e->facts;
     const bool rays12 = e->n_nominal == 12 && e->R == 12, rays16 = e->n_nominal == 16 && e->R == 17, rays32 = e->n_nominal == 32 && e->R == 33;
     if (!(rays12 || rays16 || rays32) || !e->opt.fast || T < 1 || T > INT_MAX) return PC_ERR_UNSUPPORTED;
     if ((gates_passed || final_obs) && T != 1) return PC_ERR_INVALID_ARG;      // (the optional outputs are pc_env_step's)
-    int max_G = 0, max_nV = 0;
-    bool all_nv28 = e->opt.nv28 != 0, all_loops = e->opt.nv28 != 0, tabs = true, all_rden = true;
-    int sum_nV = 0;
-    for (const TrackHdr& h : e->hdr_host) {
-        max_G = std::max(max_G, h.G);
-        max_nV = std::max(max_nV, h.nV);
-        sum_nV += h.nV;
-        tabs = tabs && h.lat_off >= 0 && (!f64 || (h.sel_ok && h.rot_off >= 0));
-        all_rden = all_rden && h.rden_off >= 0;
-        all_nv28 = all_nv28 && h.nV == 28 && h.n_chain == 26 && h.brk2 == 13 && h.vtxp_off >= 0;   // big_track's layout: two loops of 12 walls
-        all_loops = all_loops && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2);
-    }
+    const bool all_nv28 = e->opt.nv28 != 0 && f.nv28, all_loops = e->opt.nv28 != 0 && f.loops;
     const int epw = e->N <= 32768 ? 128 : 256;      // (one wave per SIMD on twice the workgroups up to 32768 envs, as pc_rollout's big form)
     // two tracks interleaved in evenly split blocks of 64 envs: de-interleaved by wave (the kernel's TWO form: 16 rays, the reference's track layouts)
     const bool two = e->track_id && e->track_block < epw && e->n_tracks == 2 && e->track_bal64 && all_loops && rays16 && e->opt.deinterleave;
-    if (!tabs || max_G > TAB_MAX_GATES || max_nV > FT_VTX_MAX || (f64 && e->f64_offgrid) || (e->track_id && e->track_block < epw && !two)) return PC_ERR_UNSUPPORTED;
+    if (!f.tabs || f.max_G > TAB_MAX_GATES || f.max_nV > FT_VTX_MAX || (f64 && e->f64_offgrid) || (e->track_id && e->track_block < epw && !two))
+        return PC_ERR_UNSUPPORTED;
     size_t lds = (size_t)(256 * e->D + (two ? 256 + 2 * ft_floats(false, true) : ft_floats(false, true))) * sizeof(float);
-    const int rden_all = 361 * (two ? sum_nV : max_nV);
-    const bool tab = table && all_rden && e->opt.rden != 0 && lds + (size_t)rden_all * sizeof(float) <= 160 * 1024;
+    const int rden_all = 361 * (two ? f.sum_nV : f.max_nV);
+    const bool tab = table && f.rden && e->opt.rden != 0 && lds + (size_t)rden_all * sizeof(float) <= 160 * 1024;
     if (tab) lds += (size_t)rden_all * sizeof(float);
     const int ts_floats = two ? ((ft_floats(false, true) + (tab ? 361 * e->hdr_host[0].nV : 0) + 3) & ~3) : 0;
     const int blocks = (int)((e->N + epw - 1) / epw);
     const int vec_ok = ((e->N * e->D) % 4 == 0 && ((uintptr_t)obs & 15) == 0) ? 1 : 0;
     EnvParams<float> prm = e->params<float>();
     prm.lg = 1;
-#define PC_STEPS(RPLV, SWPV, TABV, LITV)                                                                                 \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)env_steps_fast_kernel<RPLV, SWPV, TABV, LITV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((env_steps_fast_kernel<RPLV, SWPV, TABV, LITV>), dim3(blocks), dim3(512), lds, st, prm, actions, (int)T, reward_scale, obs, \
-                           reward, term, trunc, epw, vec_ok, gates_passed, final_obs, ts_floats);                        \
-    } while (0)
-#define PC_STEPS_T(RPLV, SWPV, LITV) do { if (tab) PC_STEPS(RPLV, SWPV, true, LITV); else PC_STEPS(RPLV, SWPV, false, LITV); } while (0)
-#define PC_STEPS2(TABV, LITV)                                                                                            \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)env_steps_fast_kernel<9, 5, TABV, LITV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((env_steps_fast_kernel<9, 5, TABV, LITV, true>), dim3(blocks), dim3(512), lds, st, prm, actions, (int)T, reward_scale, obs, \
-                           reward, term, trunc, epw, vec_ok, gates_passed, final_obs, ts_floats);                        \
-    } while (0)
-    if (two) { PC_FULL(if (f64) { if (tab) PC_STEPS2(true, true); else PC_STEPS2(false, true); } else { if (tab) PC_STEPS2(true, false); else PC_STEPS2(false, false); }); }
-    else if (rays16 && all_nv28) { if (f64) PC_DEV(3, PC_STEPS_T(9, 7, true)); else PC_DEV(0, PC_STEPS_T(9, 7, false)); }
-    else if (rays16) { PC_FULL(if (f64) PC_STEPS_T(9, 0, true); else PC_STEPS_T(9, 0, false)); }
-    else if (rays12) { PC_FULL(if (f64) PC_STEPS_T(6, 0, true); else PC_STEPS_T(6, 0, false)); }
-    else { PC_FULL(if (f64) PC_STEPS_T(17, 0, true); else PC_STEPS_T(17, 0, false)); }
-#undef PC_STEPS2
-#undef PC_STEPS_T
-#undef PC_STEPS
-    HIPCHK(hipGetLastError());
+    int (*run)(bool, int, int, size_t, hipStream_t, const StepsFastArgs&) = nullptr;
+    if (two) PC_FULL(run = f64 ? run_steps_fast<9, 5, true, true> : run_steps_fast<9, 5, false, true>);
+    else if (rays16 && all_nv28) { if (f64) PC_DEV(3, run = run_steps_fast<9, 7, true>); else PC_DEV(0, run = run_steps_fast<9, 7, false>); }
+    else if (rays16) PC_FULL(run = f64 ? run_steps_fast<9, 0, true> : run_steps_fast<9, 0, false>);
+    else if (rays12) PC_FULL(run = f64 ? run_steps_fast<6, 0, true> : run_steps_fast<6, 0, false>);
+    else PC_FULL(run = f64 ? run_steps_fast<17, 0, true> : run_steps_fast<17, 0, false>);
+    const int rc = run(tab, e->device, blocks, lds, st, {prm, actions, (int)T, reward_scale, obs, reward, term, trunc, epw, vec_ok, gates_passed, final_obs,
+                                                         ts_floats});
+    if (rc != PC_OK) return rc;
     e->last_step_kernel = tab ? PC_STEP_K1F_TABLE : PC_STEP_K1F;
     return PC_OK;
 }
@@ -350,6 +360,83 @@ static int step_generic_launch(pc_env* e, const int64_t* actions, double reward_
 #undef PC_CASE
     HIPCHK(hipGetLastError());
     return PC_OK;
+}
+
+// policy_kernel's arguments, handed by policy_act_impl to the instance it picks (`split`: the SPLIT instance)
+using PolicyArgs = std::tuple<const float*, int64_t, int, int, const float*, uint64_t, uint64_t, const uint64_t*, int64_t*, float*, float*, float*, float*>;
+template <int KS, int PREC>
+static int run_policy(bool split, int device, int blocks, size_t lds, hipStream_t st, const PolicyArgs& args) {
+    return std::apply([&](auto... a) {
+        return split ? launch_lds<policy_kernel<KS, true, PREC>>(device, blocks, lds, st, a...)
+                     : launch_lds<policy_kernel<KS, false, PREC>>(device, blocks, lds, st, a...);
+    }, args);
+}
+template <int PREC>
+static auto policy_run_for(int KS) { return KS == 5 ? run_policy<5, PREC> : KS == 6 ? run_policy<6, PREC> : run_policy<10, PREC>; }
+
+// one pc_rollout call's arguments, as the rollout kernels take them
+struct RolloutIO {
+    const float* image;
+    int A, T;
+    double reward_scale;
+    uint64_t seed, offset;
+    const uint64_t* offset_dev;
+    float *obs_buf, *act_buf, *rew_buf, *val_buf, *term_buf, *trunc_buf, *logprob_buf, *next_obs, *next_term, *next_trunc, *last_value, *reward_sum;
+};
+
+// what pc_rollout launches (plan_rollout): the kernel instance, through the launcher of its family (roll_big / roll_small / roll_f64), its grid
+// and LDS bytes, and the launch's own arguments
+struct RolloutPlan {
+    int (*launch)(const pc_env*, const RolloutPlan&, const RolloutIO&, hipStream_t) = nullptr;
+    int blocks = 0;
+    size_t lds = 0;
+    int rden_lds = 0;   // floats of the 1/den table staged in LDS (0: none)
+    int epw = 0;        // envs per workgroup (rollout_kernel, rollout_f64_kernel)
+    int lg = 1;         // EnvParams::lg
+    int vec_ok = 0;     // 16-byte stores of the observation rows
+    int kernel = 0;     // PC_KERNEL_*: what pc_env_last_rollout_kernel reports
+};
+
+template <int KS, int RPL, int PREC, int MODE, bool LIT = false, int LGE = 1>
+static int roll_big(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, hipStream_t st) {
+    EnvParams<float> prm = e->params<float>();
+    prm.lg = p.lg;
+    return launch_lds<rollout_kernel<KS, RPL, PREC, MODE, LIT, LGE>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed,
+                                                                      c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf, c.term_buf,
+                                                                      c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.rden_lds,
+                                                                      p.epw, p.vec_ok, c.last_value, c.reward_sum);
+}
+
+template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false>
+static int roll_small(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, hipStream_t st) {
+    EnvParams<float> prm = e->params<float>();
+    prm.lg = p.lg;
+    return launch_lds<rollout_small_kernel<KS, RPL, PREC, MODE, EPW, LIT>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale,
+                                                                            c.seed, c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf,
+                                                                            c.term_buf, c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term,
+                                                                            c.next_trunc, p.rden_lds, p.vec_ok, c.last_value, c.reward_sum);
+}
+
+template <int KS, int RPL, int PREC, bool SEL>
+static int roll_f64(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, hipStream_t st) {
+    EnvParams<double> prm = e->params<double>();
+    prm.lg = p.lg;
+    return launch_lds<rollout_f64_kernel<KS, RPL, PREC, SEL>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed, c.offset,
+                                                               c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf, c.term_buf, c.trunc_buf,
+                                                               c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.epw, c.last_value, c.reward_sum);
+}
+
+// rollout_kernel's generic mode (0) or fast mode (1; 2: with the 1/den table in LDS)
+template <int KS, int RPL, int PREC>
+static auto roll_big_mode(int mode) { return mode == 2 ? roll_big<KS, RPL, PREC, 2> : mode == 1 ? roll_big<KS, RPL, PREC, 1> : roll_big<KS, RPL, PREC, 0>; }
+
+// rollout_small_kernel's generic mode (0) or fast mode (1: the small form takes the 1/den table as a run-time branch) at 32 envs per workgroup,
+// or the fast mode at 16 (`epw16`: the split forms, at most five ray slots per lane)
+template <int KS, int RPL, int PREC>
+static auto roll_small_mode(int mode, bool epw16) {
+    if constexpr (PREC != 0 && RPL <= 5)
+        if (epw16) return roll_small<KS, RPL, PREC, 1, 16>;
+    return mode ? roll_small<KS, RPL, PREC, 1, 32> : roll_small<KS, RPL, PREC, 0, 32>;
 }
 
 extern "C" {
@@ -826,6 +913,17 @@ static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8
     (void)hipFree(d_sc);
     for (int k = 0; k < e->n_tracks; ++k) e->hdr_host[k].start_collides = sc[k];
     HIPCHK(hipMemcpy(e->hdr, e->hdr_host.data(), e->n_tracks * sizeof(TrackHdr), hipMemcpyHostToDevice));
+    pc_env::TrackFacts& tf = e->facts;
+    for (const TrackHdr& h : e->hdr_host) {
+        tf.max_G = std::max(tf.max_G, h.G);
+        tf.max_nV = std::max(tf.max_nV, h.nV);
+        tf.sum_nV += h.nV;
+        tf.tabs = tf.tabs && h.lat_off >= 0 && (!f64 || (h.sel_ok && h.rot_off >= 0));
+        tf.rden = tf.rden && h.rden_off >= 0;
+        tf.sel = tf.sel && h.sel_ok;
+        tf.nv28 = tf.nv28 && h.nV == 28 && h.n_chain == 26 && h.brk2 == 13 && h.vtxp_off >= 0;
+        tf.loops = tf.loops && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2);
+    }
     return PC_OK;
 }
 
@@ -1288,34 +1386,10 @@ static int policy_act_impl(int device, int prec, int split_mode, const float* ob
     const int64_t chunks = split ? (N + 31) / 32 : (N + 255) / 256;
     const int blocks = (int)(chunks < cus ? chunks : cus);  // one ~100-KB-LDS workgroup per CU, persistent over env chunks
     hipStream_t st = (hipStream_t)stream;
-#define PC_POL(KSV, SPL, PRC)                                                                                            \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (device >= 64 || !attr_set[device]) {                                                                         \
-            HIPCHK(hipFuncSetAttribute((const void*)policy_kernel<KSV, SPL, PRC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (device < 64) attr_set[device] = true;                                                                    \
-        }                                                                                                                \
-        hipLaunchKernelGGL((policy_kernel<KSV, SPL, PRC>), dim3(blocks), dim3(512), lds, st, obs, N, D, A, image, seed, offset, offset_dev, \
-                           action, action_f32, logprob, value, logits_out);                                              \
-    } while (0)
-    if (prec == 1) {
-        PC_FULL(if (split) { if (KS == 5) PC_POL(5, true, 1); else if (KS == 6) PC_POL(6, true, 1); else PC_POL(10, true, 1); }
-                else { if (KS == 5) PC_POL(5, false, 1); else if (KS == 6) PC_POL(6, false, 1); else PC_POL(10, false, 1); });
-    } else if (prec == 2) {
-        if (split) { if (KS == 5) PC_FULL(PC_POL(5, true, 2)); else if (KS == 6) PC_POL(6, true, 2); else PC_POL(10, true, 2); }
-        else { if (KS == 5) PC_FULL(PC_POL(5, false, 2)); else if (KS == 6) PC_POL(6, false, 2); else PC_POL(10, false, 2); }
-    } else if (split) {
-        PC_FULL(if (KS == 5) PC_POL(5, true, 0);
-                else if (KS == 6) PC_POL(6, true, 0);
-                else PC_POL(10, true, 0));
-    } else {
-        PC_FULL(if (KS == 5) PC_POL(5, false, 0);
-                else if (KS == 6) PC_POL(6, false, 0);
-                else PC_POL(10, false, 0));
-    }
-#undef PC_POL
-    HIPCHK(hipGetLastError());
-    return PC_OK;
+    int (*run)(bool, int, int, size_t, hipStream_t, const PolicyArgs&) = nullptr;
+    if (prec == 2 && KS != 5) run = KS == 6 ? run_policy<6, 2> : run_policy<10, 2>;     // (what a quick build keeps)
+    else PC_FULL(run = prec == 2 ? run_policy<5, 2> : prec == 1 ? policy_run_for<1>(KS) : policy_run_for<0>(KS));
+    return run(split, device, blocks, lds, st, {obs, N, D, A, image, seed, offset, offset_dev, action, action_f32, logprob, value, logits_out});
 }
 
 int pc_policy_pack(const pc_policy* p, const float* aW1, const float* ab1, const float* aW2, const float* ab2, const float* cW1,
@@ -1396,387 +1470,158 @@ int pc_clip_adam_advanced(int device, float* param, const float* grad, float* ex
     return PC_OK;
 }
 
-// pc_rollout for PC_DTYPE_F64 handles: K9d, rollout_f64_kernel (the bit-exact env inside the persistent launch).  Discrete(9), the
-// split-operand policy forms, 12 or 16 nominal rays (6 / 9 ray slots per lane); anything else is
-// PC_ERR_UNSUPPORTED and runs through the per-step kernels, which fill the same buffers bit for bit.
-static int rollout_f64_impl(pc_env* e, int prec_request, const float* image, int A, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
-                            const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
-                            float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
-                            float* reward_sum, void* stream) {
-    if (A != 9) return PC_ERR_UNSUPPORTED;
-    // mixed tracks interleaved inside a wave (no aligned block of 32 envs on one track): the generic kernel K9d, whose env step runs once
-    // per distinct track id of a wave; the literal forms stage ONE track's tables per workgroup
+// pc_rollout's choice for this handle and call: PC_OK with `p` filled, or PC_ERR_UNSUPPORTED (the caller then runs the per-step kernels,
+// which fill the same buffers bit for bit).  The rules run in order of preference.  F32 and F64 handles share the two-track and the
+// 16-envs-per-wave forms (LIT: an F64 handle, whose env step is the literal form); every other rule belongs to one dtype.
+static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPlan& p) {
+    const bool lit = e->dtype == PC_DTYPE_F64;
+    if (lit ? A != 9 : (A < 1 || A > 15)) return PC_ERR_UNSUPPORTED;
+    const RolloutOpts& o = e->opt;
+    const pc_env::TrackFacts& f = e->facts;
+    const bool all_nv28 = o.nv28 != 0 && f.nv28, all_loops = o.nv28 != 0 && f.loops;
+    // mixed tracks interleaved inside a wave (no aligned block of 32 envs on one track; car_env.py:621-628 makes that legal): F32 handles
+    // take the BIG form's generic mode, whose env step runs once per distinct track id of a wave (K1's waterfall), F64 handles the generic
+    // kernel K9d -- the fast and literal forms stage ONE track's tables per workgroup, and the small form's sweep parts meet across
+    // workgroup barriers that a per-wave loop cannot contain
     const bool interleaved = e->track_id && !e->track_blocks32;
     const int KS = policy_ks(e->D);
-    const int prec = policy_prec(prec_request, e->D, A);
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int rpl = (e->R + 1) / 2;
-    const int epw = e->opt.epw_override >= 128 ? e->opt.epw_override : (e->N <= g_rollout_epw128_max ? 128 : 256);
-    const int blocks = (int)((e->N + epw - 1) / epw);
-    hipStream_t st = (hipStream_t)stream;
-    // ---- the SELECTOR form: K9 itself (rollout_kernel<..., LIT>) -- the float32 sweep picks each ray's wall, the reference's literal
-    // float64 arithmetic measures it (env_step_fast's literal form, lit_fast / lit_careful).  What it needs: every track inside the
-    // selector's limits with its rotation table built, every env's rotation a row of that table for the rest of its episode
-    // (f64_offgrid), the fast modes' shape (12, 16 or 32 nominal rays, fp16 x 2 policy arithmetic, PC_OPT_ROLLOUT_FAST not 0) and LDS
-    // for the tables and (12 / 16 rays) the 1/den table.  The sweep is chosen as for F32 handles: chain-packed for two equal loops of 13 vertices
-    // (big_track.json) or, mixed, of 13 or 9; the generic sweeps for any other track.  Anything else: the filter form below.
-    {
-        int max_G = 0, max_nV = 0;
-        bool all_nv28 = e->opt.nv28 != 0, all_loops = e->opt.nv28 != 0, tabs = true;
-        for (const TrackHdr& h : e->hdr_host) {
-            max_G = std::max(max_G, h.G);
-            max_nV = std::max(max_nV, h.nV);
-            tabs = tabs && h.sel_ok && h.rot_off >= 0 && h.lat_off >= 0;
-            all_nv28 = all_nv28 && h.nV == 28 && h.n_chain == 26 && h.brk2 == 13 && h.vtxp_off >= 0;
-            all_loops = all_loops && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2);
-        }
-        const int img = polx_image_dwords(prec, pol_ng(KS));
-        const bool rays16 = KS == 6 && rpl == 9 && e->n_nominal == 16, rays12 = KS == 5 && rpl == 6 && e->n_nominal == 12;
-        const bool rays33 = KS == 10 && rpl == 17 && e->n_nominal == 32;
-        int rden_lds = rays33 ? 0 : 361 * max_nV;      // (33 rays: no room for the table -- the sweep forms 1/den itself, as for F32 handles)
-        size_t lds_sel = (size_t)k9_fast_lds_floats(img, 32, e->D, !rays33, rden_lds) * sizeof(float);
-        if (rden_lds && lds_sel > 160 * 1024) {        // ... and so does a 12 / 16-ray track whose table does not fit (more than ~36 chain vertices)
-            rden_lds = 0;
-            lds_sel = (size_t)k9_fast_lds_floats(img, 32, e->D, true, 0) * sizeof(float);
-        }
-        if (prec == 0) {
-            // THE STRICTEST CELL: float64 env (the literal form) AND the policy GEMMs as the exact fp32 chain (v_mfma_f32_16x16x4_f32) -- every
-            // number of the rollout in the reference's own arithmetic -- as one persistent launch: K9's literal form with the fp32 weight
-            // image (16 -> 17 rays, the big form, the generic sweeps; the fp32 image leaves no room for the 1/den table, as for F32
-            // handles).  Other shapes: the per-step kernels.
-            const int img0 = pol_image_padded(KS);
-            const size_t lds0 = (size_t)k9_fast_lds_floats(img0, 32, e->D, true, 0) * sizeof(float);
-            if (!(tabs && rays16 && !e->f64_offgrid && !interleaved && e->D >= 17 && max_G <= TAB_MAX_GATES && max_nV <= FT_VTX_MAX && e->opt.fast &&
-                  (!e->track_id || e->track_block >= epw) && lds0 <= 160 * 1024))
-                return PC_ERR_UNSUPPORTED;
-            const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-            EnvParams<float> prm = e->params<float>();
-            prm.lg = 1;
-#ifndef PC_DEV_MIN
-            static bool attr_set[64] = {false};
-            if (e->device >= 64 || !attr_set[e->device]) {
-                HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 9, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                if (e->device < 64) attr_set[e->device] = true;
-            }
-#endif
-            PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 9, 0, 1, true>), dim3(blocks), dim3(512), lds0, st, prm, image, A, (int)T, reward_scale, seed, offset,
-                                       offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc,
-                                       0, epw, vec_ok, last_value, reward_sum));
-            HIPCHK(hipGetLastError());
-            e->last_kernel = PC_KERNEL_K9_LITERAL;
+    const int img = prec ? polx_image_dwords(prec, pol_ng(KS)) : pol_image_padded(KS);
+    // 12 / 16 / 32 nominal rays: 12 / 17 / 33 actual, D = 18 / 23 / 39 (KS = 5 / 6 / 10), 6 / 9 / 17 ray slots on two lanes per env
+    const bool rays12 = e->n_nominal == 12, rays16 = e->n_nominal == 16, rays32 = e->n_nominal == 32;
+    const int epw = o.epw_override >= 128 ? o.epw_override : (e->N <= g_rollout_epw128_max ? 128 : 256);   // big form: envs per workgroup
+    p.epw = epw;
+    p.blocks = (int)((e->N + epw - 1) / epw);
+    p.vec_ok = vec_ok;
+    if (lit && prec == 0) {
+        // THE STRICTEST CELL: float64 env (the literal form) AND the policy GEMMs as the exact fp32 chain (v_mfma_f32_16x16x4_f32) -- every
+        // number of the rollout in the reference's own arithmetic -- as one persistent launch: K9's literal form with the fp32 weight
+        // image (16 -> 17 rays, the big form, the generic sweeps; the fp32 image leaves no room for the 1/den table, as for F32
+        // handles).  Other shapes: the per-step kernels.
+        p.lds = (size_t)k9_fast_lds_floats(img, 32, e->D, true, 0) * sizeof(float);
+        if (!(f.tabs && rays16 && !e->f64_offgrid && !interleaved && e->D >= 17 && f.max_G <= TAB_MAX_GATES && f.max_nV <= FT_VTX_MAX && o.fast &&
+              (!e->track_id || e->track_block >= epw) && p.lds <= 160 * 1024))
+            return PC_ERR_UNSUPPORTED;
+        PC_FULL(p.launch = roll_big<6, 9, 0, 1, true>);
+        p.kernel = PC_KERNEL_K9_LITERAL;
+        return PC_OK;
+    }
+    if (!lit && interleaved && o.form == 1) return PC_ERR_UNSUPPORTED;
+    const bool want_m = o.form == 4 || (o.form < 0 && o.epw_override == 0 && e->N > PC_SPLIT_MAX_ENVS && e->N <= PC_MEDIUM_MAX_ENVS);
+    // ---- tracks interleaved inside the waves, the reference's own pair (two tracks, each two equal loops of 13 or 9 chain vertices,
+    // 16 -> 17 rays, fp16 x 2): both tracks' tables in LDS, the table-driven env step once per track of a wave (mode 6); where every block
+    // is split evenly between the two, the block's two waves de-interleave it (mode 7).  16 envs per wave (4 lanes per env) where the
+    // 16-envs-per-wave form is wanted, as for single-track and block-mixed batches of that size: two waves on every SIMD
+    if (interleaved && o.fast && o.nv28 != 0 && e->n_tracks == 2 && rays16 && A == 9 && prec == 2 && e->D >= 17 && e->D <= 40 && f.loops &&
+        f.max_nV <= FT_VTX_MAX && f.max_G <= TAB_MAX_GATES && (!lit || (f.tabs && !e->f64_offgrid))) {
+        const int ts6 = (ft_floats(false, true) + 3) & ~3;
+        const size_t lds6 = (size_t)k9_fast_lds_floats(img, 32, e->D, true, ts6) * sizeof(float);
+        if (lds6 <= 160 * 1024 && want_m) {
+            if (e->track_bal32 && o.deinterleave) PC_FULL(p.launch = lit ? roll_big<6, 5, 2, 7, true, 2> : roll_big<6, 5, 2, 7, false, 2>);
+            else PC_FULL(p.launch = lit ? roll_big<6, 5, 2, 6, true, 2> : roll_big<6, 5, 2, 6, false, 2>);
+            p.blocks = (int)((e->N + 127) / 128);
+            p.lds = (size_t)k9_fast_lds_floats(img, 16, e->D, true, ts6) * sizeof(float);
+            p.epw = 128;
+            p.lg = 2;
+            p.kernel = lit ? PC_KERNEL_K9M_LITERAL : PC_KERNEL_K9M;
             return PC_OK;
         }
-        // tracks interleaved inside the waves: the two-track fast form of F32 handles (rollout_impl) with the literal env step
-        if (interleaved && prec == 2 && tabs && rays16 && !e->f64_offgrid && e->opt.fast && e->opt.nv28 != 0 && e->n_tracks == 2 && all_loops &&
-            max_G <= TAB_MAX_GATES && max_nV <= FT_VTX_MAX && e->D >= 17) {
-            const int ts6 = (ft_floats(false, true) + 3) & ~3;
-            const size_t lds6 = (size_t)k9_fast_lds_floats(img, 32, e->D, true, ts6) * sizeof(float);
-            if (lds6 <= 160 * 1024 && (e->opt.form == 4 || (e->opt.form < 0 && e->opt.epw_override == 0 && e->N > PC_SPLIT_MAX_ENVS && e->N <= PC_MEDIUM_MAX_ENVS))) {
-                const int vec6 = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;      // 16 envs per wave
-                const size_t lds6m = (size_t)k9_fast_lds_floats(img, 16, e->D, true, ts6) * sizeof(float);
-                EnvParams<float> prm6 = e->params<float>();
-                prm6.lg = 2;
-#ifndef PC_DEV_MIN
-                static bool attr6m[64] = {false};
-                if (e->device >= 64 || !attr6m[e->device]) {
-                    HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, 6, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    if (e->device < 64) attr6m[e->device] = true;
-                }
-#endif
-                if (e->track_bal32 && e->opt.deinterleave) {
-#ifndef PC_DEV_MIN
-                    static bool attr7m[64] = {false};
-                    if (e->device >= 64 || !attr7m[e->device]) {
-                        HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, 7, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        if (e->device < 64) attr7m[e->device] = true;
-                    }
-#endif
-                    PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 5, 2, 7, true, 2>), dim3((int)((e->N + 127) / 128)), dim3(512), lds6m, st, prm6, image, A, (int)T, reward_scale, seed,
-                                               offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, 128,
-                                               vec6, last_value, reward_sum));
-                } else
-                PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 5, 2, 6, true, 2>), dim3((int)((e->N + 127) / 128)), dim3(512), lds6m, st, prm6, image, A, (int)T, reward_scale, seed,
-                                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, 128,
-                                           vec6, last_value, reward_sum));
-                HIPCHK(hipGetLastError());
-                e->last_kernel = PC_KERNEL_K9M_LITERAL;
-                return PC_OK;
-            }
-            if (lds6 <= 160 * 1024) {
-                const int vec6 = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-                EnvParams<float> prm6 = e->params<float>();
-                prm6.lg = 1;
-#ifndef PC_DEV_MIN
-                static bool attr6[64] = {false};
-                if (e->device >= 64 || !attr6[e->device]) {
-                    HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 9, 2, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    if (e->device < 64) attr6[e->device] = true;
-                }
-#endif
-                if (e->track_bal64 && e->opt.deinterleave) {
-#ifndef PC_DEV_MIN
-                    static bool attr7[64] = {false};
-                    if (e->device >= 64 || !attr7[e->device]) {
-                        HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 9, 2, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        if (e->device < 64) attr7[e->device] = true;
-                    }
-#endif
-                    PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 9, 2, 7, true>), dim3(blocks), dim3(512), lds6, st, prm6, image, A, (int)T, reward_scale, seed, offset,
-                                               offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, epw,
-                                               vec6, last_value, reward_sum));
-                } else
-                PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 9, 2, 6, true>), dim3(blocks), dim3(512), lds6, st, prm6, image, A, (int)T, reward_scale, seed, offset,
-                                           offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, epw,
-                                           vec6, last_value, reward_sum));
-                HIPCHK(hipGetLastError());
-                e->last_kernel = PC_KERNEL_K9_LITERAL;
-                return PC_OK;
-            }
+        if (lds6 <= 160 * 1024) {
+            if (e->track_bal64 && o.deinterleave) PC_FULL(p.launch = lit ? roll_big<6, 9, 2, 7, true> : roll_big<6, 9, 2, 7>);
+            else PC_FULL(p.launch = lit ? roll_big<6, 9, 2, 6, true> : roll_big<6, 9, 2, 6>);
+            p.lds = lds6;
+            p.kernel = lit ? PC_KERNEL_K9_LITERAL : PC_KERNEL_K9;
+            return PC_OK;
         }
-        const bool shape = (rays16 || rays12 || rays33) && prec == 2 && e->D >= 17 && e->D <= 40 && max_G <= TAB_MAX_GATES &&
-                           max_nV <= FT_VTX_MAX && e->opt.fast && e->opt.rden != 0 && (!e->track_id || e->track_block >= epw) &&
-                           lds_sel <= 160 * 1024;
-        // ... and up to PC_SPLIT_MAX_ENVS envs at 12 / 16 rays the SMALL form (K9s: 16 envs per workgroup up to 4096 envs, wave-owned envs -- env_step_wave's
-        // literal form --, else 32 with the sweep parts on four waves), chosen as for F32 handles (PC_OPT_ROLLOUT_FORM / _EPW)
-        const RolloutOpts& o = e->opt;
+    }
+    // K9's literal form (F64 handles) stages the 1/den table where it fits: 12 / 16 rays up to ~36 chain vertices (33 rays: no room -- the
+    // sweep forms 1/den itself, as for F32 handles)
+    int rden_sel = rays32 ? 0 : 361 * f.max_nV;
+    size_t lds_sel = (size_t)k9_fast_lds_floats(img, 32, e->D, !rays32, rden_sel) * sizeof(float);
+    if (rden_sel && lds_sel > 160 * 1024) {
+        rden_sel = 0;
+        lds_sel = (size_t)k9_fast_lds_floats(img, 32, e->D, true, 0) * sizeof(float);
+    }
+    // ---- the 16-envs-per-wave form (rollout_kernel<6, 5, 2, MD, LIT, 2>): 17 rays, fp16 x 2, the chain-packed sweeps' track layouts, the
+    // 1/den table in LDS; automatic between PC_SPLIT_MAX_ENVS and PC_MEDIUM_MAX_ENVS envs, PC_OPT_ROLLOUT_FORM = 4 at any size.  (Never
+    // a batch of the small form, whose rules below it therefore does not overtake.)
+    {
+        const int rden_m = 361 * f.max_nV;
+        const size_t lds_m = (size_t)k9_fast_lds_floats(img, 16, e->D, true, rden_m) * sizeof(float);
+        if (want_m && rays16 && prec == 2 && A == 9 && e->D >= 17 && e->D <= 40 && f.max_G <= TAB_MAX_GATES && f.max_nV <= FT_VTX_MAX && o.fast &&
+            o.rden != 0 && (all_nv28 || all_loops) && (!e->track_id || e->track_block >= 128) && lds_m <= 160 * 1024 &&
+            (!lit || (f.tabs && !e->f64_offgrid && (!e->track_id || e->track_block >= epw) && lds_sel <= 160 * 1024))) {
+            if (lit) { if (all_nv28) PC_DEV(8, p.launch = roll_big<6, 5, 2, 3, true, 2>); else PC_FULL(p.launch = roll_big<6, 5, 2, 5, true, 2>); }
+            else { if (all_nv28) PC_DEV(7, p.launch = roll_big<6, 5, 2, 3, false, 2>); else PC_FULL(p.launch = roll_big<6, 5, 2, 5, false, 2>); }
+            p.blocks = (int)((e->N + 127) / 128);
+            p.lds = lds_m;
+            p.rden_lds = rden_m;
+            p.epw = 128;
+            p.lg = 2;
+            p.kernel = lit ? PC_KERNEL_K9M_LITERAL : PC_KERNEL_K9M;
+            return PC_OK;
+        }
+    }
+    if (lit) {
+        // ---- the SELECTOR form: K9 itself (rollout_kernel<..., LIT>) -- the float32 sweep picks each ray's wall, the reference's literal
+        // float64 arithmetic measures it (env_step_fast's literal form, lit_fast / lit_careful).  What it needs: every track inside the
+        // selector's limits with its rotation table built, every env's rotation a row of that table for the rest of its episode
+        // (f64_offgrid), the fast modes' shape (12, 16 or 32 nominal rays, fp16 x 2 policy arithmetic, PC_OPT_ROLLOUT_FAST not 0) and LDS
+        // for the tables and (12 / 16 rays) the 1/den table.  The sweep is chosen as for F32 handles: chain-packed for two equal loops of 13
+        // vertices (big_track.json) or, mixed, of 13 or 9; the generic sweeps for any other track.  Up to PC_SPLIT_MAX_ENVS envs at 12 / 16
+        // rays the SMALL form (K9s: 16 envs per workgroup up to 4096 envs, wave-owned envs -- env_step_wave's literal form --, else 32 with
+        // the sweep parts on four waves), chosen as for F32 handles (PC_OPT_ROLLOUT_FORM / _EPW).  Anything else: the filter form below.
         const bool small = o.form == 1 || (o.form < 0 && e->N <= PC_SPLIT_MAX_ENVS);
         const bool epw16 = o.epw_override == 16 || (o.epw_override != 32 && e->N <= 4096);
-        const int rden_small = 361 * max_nV;
+        const int rden_small = 361 * f.max_nV;
         size_t lds_small = (size_t)(img + 8 * 32 * 17 + 32 * 40 + 32 + 128 + ft_floats(true, true)) * sizeof(float);
         const int rden_small_lds = (o.rden != 0 && lds_small + (size_t)rden_small * sizeof(float) <= 160 * 1024) ? rden_small : 0;
         lds_small += (size_t)rden_small_lds * sizeof(float);
-        const bool shape_small = (rays16 || rays12) && prec == 2 && small && max_G <= TAB_MAX_GATES && max_nV <= FT_VTX_MAX && o.fast &&
-                                 lds_small <= 160 * 1024;
-        if (tabs && shape_small && !e->f64_offgrid && !interleaved) {
-            const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-            EnvParams<float> prm = e->params<float>();
-            prm.lg = 2;
-#define PC_ROLLS_LIT(KSV, RPLV, EPWV)                                                                                    \
-    do {                                                                                                                 \
-        const int blocks_small = (int)((e->N + EPWV - 1) / EPWV);                                                        \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_small_kernel<KSV, RPLV, 2, 1, EPWV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_small_kernel<KSV, RPLV, 2, 1, EPWV, true>), dim3(blocks_small), dim3(512), lds_small, st, prm, image, A, (int)T, \
-                           reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, \
-                           next_obs, next_term, next_trunc, rden_small_lds, vec_ok, last_value, reward_sum);             \
-    } while (0)
-            if (rays16) {
-                if (epw16) PC_DEV(6, PC_ROLLS_LIT(6, 5, 16));      // wave-owned envs (env_step_wave)
-                else PC_FULL(PC_ROLLS_LIT(6, 5, 32));              // four sweep parts = waves (env_step_fast<..., 2, 4>)
-            } else {                                               // 12 rays: three ray slots per lane
-                if (epw16) PC_FULL(PC_ROLLS_LIT(5, 3, 16));
-                else PC_FULL(PC_ROLLS_LIT(5, 3, 32));
-            }
-#undef PC_ROLLS_LIT
-            HIPCHK(hipGetLastError());
-            e->last_kernel = PC_KERNEL_K9S_LITERAL;
+        if (f.tabs && !e->f64_offgrid && !interleaved && (rays16 || rays12) && prec == 2 && small && f.max_G <= TAB_MAX_GATES &&
+            f.max_nV <= FT_VTX_MAX && o.fast && lds_small <= 160 * 1024) {
+            if (rays16 && epw16) PC_DEV(6, p.launch = (roll_small<6, 5, 2, 1, 16, true>));    // wave-owned envs (env_step_wave)
+            else if (rays16) PC_FULL(p.launch = (roll_small<6, 5, 2, 1, 32, true>));         // four sweep parts = waves (env_step_fast<..., 2, 4>)
+            else PC_FULL(p.launch = epw16 ? roll_small<5, 3, 2, 1, 16, true> : roll_small<5, 3, 2, 1, 32, true>);     // 12 rays: three ray slots per lane
+            p.blocks = (int)(epw16 ? (e->N + 15) / 16 : (e->N + 31) / 32);
+            p.lds = lds_small;
+            p.rden_lds = rden_small_lds;
+            p.lg = 2;
+            p.kernel = PC_KERNEL_K9S_LITERAL;
             return PC_OK;
         }
-        // ... between PC_SPLIT_MAX_ENVS and PC_MEDIUM_MAX_ENVS envs at 16 rays the 16-envs-per-wave form (as for F32 handles)
-        {
-            const bool want = o.form == 4 || (o.form < 0 && o.epw_override == 0 && e->N > PC_SPLIT_MAX_ENVS && e->N <= PC_MEDIUM_MAX_ENVS);
-            const int rden_m = 361 * max_nV;
-            const size_t lds_m = (size_t)k9_fast_lds_floats(img, 16, e->D, true, rden_m) * sizeof(float);
-            if (want && tabs && shape && rays16 && !e->f64_offgrid && !interleaved && (all_nv28 || all_loops) && (!e->track_id || e->track_block >= 128) &&
-                lds_m <= 160 * 1024) {
-                const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-                EnvParams<float> prm = e->params<float>();
-                prm.lg = 2;
-                const int blocks_m = (int)((e->N + 127) / 128);
-#define PC_ROLL_MEDL(MD)                                                                                                 \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, MD, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_kernel<6, 5, 2, MD, true, 2>), dim3(blocks_m), dim3(512), lds_m, st, prm, image, A, (int)T, reward_scale, seed, \
-                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,  \
-                           next_term, next_trunc, rden_m, 128, vec_ok, last_value, reward_sum);                          \
-    } while (0)
-                if (all_nv28) PC_DEV(8, PC_ROLL_MEDL(3)); else PC_FULL(PC_ROLL_MEDL(5));
-#undef PC_ROLL_MEDL
-                HIPCHK(hipGetLastError());
-                e->last_kernel = PC_KERNEL_K9M_LITERAL;
-                return PC_OK;
-            }
-        }
-        if (tabs && shape && !e->f64_offgrid && !interleaved) {
-            const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-            EnvParams<float> prm = e->params<float>();
-            prm.lg = 1;
-#define PC_ROLL_LIT(KSV, RPLV, MD)                                                                                       \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<KSV, RPLV, 2, MD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_kernel<KSV, RPLV, 2, MD, true>), dim3(blocks), dim3(512), lds_sel, st, prm, image, A, (int)T, reward_scale, seed, \
-                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,  \
-                           next_term, next_trunc, rden_lds, epw, vec_ok, last_value, reward_sum);                        \
-    } while (0)
-            if (rays16 && all_nv28) PC_DEV(3, PC_ROLL_LIT(6, 9, 3));            // big_track.json's layout
-            else if (rays16 && all_loops) PC_FULL(PC_ROLL_LIT(6, 9, 5));        // ... mixed with track.json's
-            else if (rays16) { PC_FULL(if (rden_lds) PC_ROLL_LIT(6, 9, 2); else PC_ROLL_LIT(6, 9, 1)); }     // any other track: the generic sweeps
-            else if (rays33) PC_DEV(5, PC_ROLL_LIT(10, 17, 1));                 // 32 -> 33 rays: no room for the 1/den table
-            else { PC_FULL(if (rden_lds) PC_ROLL_LIT(5, 6, 2); else PC_ROLL_LIT(5, 6, 1)); }                // 12 rays
-#undef PC_ROLL_LIT
-            HIPCHK(hipGetLastError());
-            e->last_kernel = PC_KERNEL_K9_LITERAL;
+        const bool shape = (rays16 || rays12 || rays32) && prec == 2 && e->D >= 17 && e->D <= 40 && f.max_G <= TAB_MAX_GATES &&
+                           f.max_nV <= FT_VTX_MAX && o.fast && o.rden != 0 && (!e->track_id || e->track_block >= epw) && lds_sel <= 160 * 1024;
+        if (f.tabs && shape && !e->f64_offgrid && !interleaved) {
+            if (rays16 && all_nv28) PC_DEV(3, p.launch = (roll_big<6, 9, 2, 3, true>));        // big_track.json's layout
+            else if (rays16 && all_loops) PC_FULL(p.launch = (roll_big<6, 9, 2, 5, true>));    // ... mixed with track.json's
+            else if (rays16) PC_FULL(p.launch = rden_sel ? roll_big<6, 9, 2, 2, true> : roll_big<6, 9, 2, 1, true>);    // any other track: the generic sweeps
+            else if (rays32) PC_DEV(5, p.launch = (roll_big<10, 17, 2, 1, true>));             // 32 -> 33 rays: no room for the 1/den table
+            else PC_FULL(p.launch = rden_sel ? roll_big<5, 6, 2, 2, true> : roll_big<5, 6, 2, 1, true>);                // 12 rays
+            p.lds = lds_sel;
+            p.rden_lds = rden_sel;
+            p.kernel = PC_KERNEL_K9_LITERAL;
             return PC_OK;
         }
+        // K9d: the generic kernel.  With PC_OPT_ROLLOUT_FAST = 0 every (ray, wall) pair is tested in float64 (the FILTER form: no float32
+        // anywhere); otherwise tracks inside the selector's limits step as the per-step kernel does (sweep over the chain in global
+        // memory, literal cast: rollout_f64_kernel<..., SEL>) -- what is left for this kernel by default are tracks too long for the
+        // LDS tables and rotations off the table; bf16 x 3 keeps the filter.
+        p.lds = (size_t)(img + 256 * (4 * KS + 1)) * sizeof(float);
+        if (p.lds > 160 * 1024) return PC_ERR_UNSUPPORTED;
+        const int rpl = (e->R + 1) / 2;
+        const bool sel = o.fast && f.sel && prec == 2;      // (the selector variant for the fp16 x 2 forms only: bf16 x 3 -- 12 rays -- keeps the filter)
+        if (KS == 5 && rpl == 6) {                         // 12 rays, D = 18
+            PC_FULL(p.launch = sel ? roll_f64<5, 6, 2, true> : prec == 2 ? roll_f64<5, 6, 2, false> : roll_f64<5, 6, 1, false>);
+        } else if (KS == 6 && rpl == 9) {                  // 16 -> 17 rays, D = 23 (bf16 x 3 there spills 3 registers: not built)
+            if (prec != 2) return PC_ERR_UNSUPPORTED;
+            if (sel) PC_FULL(p.launch = (roll_f64<6, 9, 2, true>)); else PC_DEV(4, p.launch = (roll_f64<6, 9, 2, false>));
+        } else return PC_ERR_UNSUPPORTED;     // (32 -> 33 rays: 17 float64 ray slots per lane beside the policy state spill 96 registers -- not built;
+                                              //  the per-step kernels run that shape)
+        p.kernel = sel ? PC_KERNEL_K9D_SELECTOR : PC_KERNEL_K9D_FILTER;
+        return PC_OK;
     }
-    const size_t lds = (size_t)(polx_image_dwords(prec, pol_ng(KS)) + 256 * (4 * KS + 1)) * sizeof(float);
-    if (lds > 160 * 1024) return PC_ERR_UNSUPPORTED;
-    // K9d: the generic kernel.  With PC_OPT_ROLLOUT_FAST = 0 every (ray, wall) pair is tested in float64 (the FILTER form: no float32
-    // anywhere); otherwise tracks inside the selector's limits step as the per-step kernel does (sweep over the chain in global
-    // memory, literal cast: rollout_f64_kernel<..., SEL>) -- what is left for this kernel by default are tracks too long for the
-    // LDS tables and rotations off the table; bf16 x 3 keeps the filter.
-    bool all_sel = true;
-    for (const TrackHdr& h : e->hdr_host) all_sel = all_sel && h.sel_ok;
-    const int sel_on = (e->opt.fast && all_sel) ? 1 : 0;
-    const EnvParams<double> prm = [&] { EnvParams<double> q = e->params<double>(); q.lg = 1; return q; }();
-#define PC_ROLLD(KSV, RPLV, PRC, SELV)                                                                                   \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_f64_kernel<KSV, RPLV, PRC, SELV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_f64_kernel<KSV, RPLV, PRC, SELV>), dim3(blocks), dim3(512), lds, st, prm, image, A, (int)T, reward_scale, seed, \
-                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,  \
-                           next_term, next_trunc, epw, last_value, reward_sum);                                          \
-    } while (0)
-    // (the selector variant for the fp16 x 2 forms only: bf16 x 3 -- 12 rays -- keeps the filter)
-    const bool sel_k = sel_on && prec == 2;
-    if (KS == 5 && rpl == 6) { PC_FULL(if (sel_k) PC_ROLLD(5, 6, 2, true); else if (prec == 2) PC_ROLLD(5, 6, 2, false); else PC_ROLLD(5, 6, 1, false)); }              // 12 rays, D = 18
-    else if (KS == 6 && rpl == 9) {                                                                                    // 16 -> 17 rays, D = 23 (bf16 x 3 there spills 3 registers: not built)
-        if (prec != 2) return PC_ERR_UNSUPPORTED;
-        if (sel_k) PC_FULL(PC_ROLLD(6, 9, 2, true)); else PC_DEV(4, PC_ROLLD(6, 9, 2, false));
-    }
-    else return PC_ERR_UNSUPPORTED;     // (32 -> 33 rays: 17 float64 ray slots per lane beside the policy state spill 96 registers -- not built;
-                                        //  the per-step kernels run that shape)
-#undef PC_ROLLD
-    HIPCHK(hipGetLastError());
-    e->last_kernel = sel_k ? PC_KERNEL_K9D_SELECTOR : PC_KERNEL_K9D_FILTER;
-    return PC_OK;
-}
-
-static int rollout_impl(pc_env* e, int prec_request, const float* image, int A, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
-                        const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
-                        float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
-                        float* reward_sum, void* stream) {
-    if (!e || !image || !obs_buf || !act_buf || !rew_buf || !val_buf || !term_buf || !trunc_buf || !logprob_buf || !next_obs ||
-        !next_term || !next_trunc || T < 1 || T > (1 << 24))
-        return PC_ERR_INVALID_ARG;
-    // mixed tracks: a wave (big form) / a workgroup (small form) steps 32 consecutive envs, which must share one track
-    if (e->dtype == PC_DTYPE_F64)
-        return rollout_f64_impl(e, prec_request, image, A, T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf,
-                                trunc_buf, logprob_buf, next_obs, next_term, next_trunc, last_value, reward_sum, stream);
-    if (e->dtype != PC_DTYPE_F32 || A < 1 || A > 15) return PC_ERR_UNSUPPORTED;
-    // mixed tracks interleaved inside a wave (no aligned block of 32 envs on one track; car_env.py:621-628 makes that legal): the BIG
-    // form's generic mode, whose env step runs once per distinct track id of a wave (K1's waterfall) -- the fast modes stage ONE track's
-    // tables per workgroup, and the small form's sweep parts meet across workgroup barriers that a per-wave loop cannot contain
-    const bool interleaved = e->track_id && !e->track_blocks32;
-    const int KS = policy_ks(e->D);
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int prec = policy_prec(prec_request, e->D, A);
-    const RolloutOpts& o = e->opt;
-    const int img = prec ? polx_image_dwords(prec, pol_ng(KS)) : pol_image_padded(KS);
-    // large batches: 256 envs per workgroup, every wave independent; small batches: 32 envs per workgroup, hidden tiles and
-    // wall-sweep parts split over the waves
-    if (interleaved && o.form == 1) return PC_ERR_UNSUPPORTED;
-    // ... and the FAST form of that layout for the reference's own pair of tracks (two tracks, each two equal loops of 13 or 9 chain
-    // vertices, 16 -> 17 rays, fp16 x 2): both tracks' tables in LDS, the table-driven env step once per track of a wave (rollout_kernel<6, 9, 2, 6>)
-    if (interleaved && o.fast && o.nv28 != 0 && e->n_tracks == 2 && policy_ks(e->D) == 6 && e->n_nominal == 16 && A == 9 && policy_prec(prec_request, e->D, A) == 2 &&
-        e->D >= 17 && e->D <= 40) {
-        bool loops2 = true;
-        int mg = 0;
-        for (const TrackHdr& h : e->hdr_host) {
-            loops2 = loops2 && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2) && h.nV <= FT_VTX_MAX;
-            mg = std::max(mg, h.G);
-        }
-        const int img6 = polx_image_dwords(2, pol_ng(6));
-        const int ts6 = (ft_floats(false, true) + 3) & ~3;
-        const size_t lds6 = (size_t)k9_fast_lds_floats(img6, 32, e->D, true, ts6) * sizeof(float);
-        if (loops2 && mg <= TAB_MAX_GATES && lds6 <= 160 * 1024) {
-            DeviceGuard guard6(e->device);
-            if (!guard6.ok) return PC_ERR_NO_DEVICE;
-            if (o.form == 4 || (o.form < 0 && o.epw_override == 0 && e->N > PC_SPLIT_MAX_ENVS && e->N <= PC_MEDIUM_MAX_ENVS)) {
-                // 16 envs per wave (4 lanes per env), as for single-track and block-mixed batches of this size: two waves on every SIMD
-                const int vec6 = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-                const size_t lds6m = (size_t)k9_fast_lds_floats(img6, 16, e->D, true, ts6) * sizeof(float);
-                EnvParams<float> prm6 = e->params<float>();
-                prm6.lg = 2;
-#ifndef PC_DEV_MIN
-                static bool attr6m[64] = {false};
-                if (e->device >= 64 || !attr6m[e->device]) {
-                    HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, 6, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    if (e->device < 64) attr6m[e->device] = true;
-                }
-#endif
-                if (e->track_bal32 && o.deinterleave) {      // every block of 32 envs split evenly: the block's two waves de-interleave it (mode 7)
-#ifndef PC_DEV_MIN
-                    static bool attr7m[64] = {false};
-                    if (e->device >= 64 || !attr7m[e->device]) {
-                        HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, 7, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        if (e->device < 64) attr7m[e->device] = true;
-                    }
-#endif
-                    PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 5, 2, 7, false, 2>), dim3((int)((e->N + 127) / 128)), dim3(512), lds6m, (hipStream_t)stream, prm6, image, A, (int)T,
-                                               reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term,
-                                               next_trunc, 0, 128, vec6, last_value, reward_sum));
-                } else
-                PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 5, 2, 6, false, 2>), dim3((int)((e->N + 127) / 128)), dim3(512), lds6m, (hipStream_t)stream, prm6, image, A, (int)T,
-                                           reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term,
-                                           next_trunc, 0, 128, vec6, last_value, reward_sum));
-                HIPCHK(hipGetLastError());
-                e->last_kernel = PC_KERNEL_K9M;
-                return PC_OK;
-            }
-            const int epw6 = o.epw_override >= 128 ? o.epw_override : (e->N <= g_rollout_epw128_max ? 128 : 256);
-            const int blocks6 = (int)((e->N + epw6 - 1) / epw6);
-            const int vec6 = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-            EnvParams<float> prm6 = e->params<float>();
-            prm6.lg = 1;
-#ifndef PC_DEV_MIN
-            static bool attr6[64] = {false};
-            if (e->device >= 64 || !attr6[e->device]) {
-                HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 9, 2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                if (e->device < 64) attr6[e->device] = true;
-            }
-#endif
-            if (e->track_bal64 && o.deinterleave) {
-#ifndef PC_DEV_MIN
-                static bool attr7[64] = {false};
-                if (e->device >= 64 || !attr7[e->device]) {
-                    HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 9, 2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    if (e->device < 64) attr7[e->device] = true;
-                }
-#endif
-                PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 9, 2, 7>), dim3(blocks6), dim3(512), lds6, (hipStream_t)stream, prm6, image, A, (int)T, reward_scale, seed, offset,
-                                           offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, epw6,
-                                           vec6, last_value, reward_sum));
-            } else
-            PC_FULL(hipLaunchKernelGGL((rollout_kernel<6, 9, 2, 6>), dim3(blocks6), dim3(512), lds6, (hipStream_t)stream, prm6, image, A, (int)T, reward_scale, seed, offset,
-                                       offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, next_term, next_trunc, 0, epw6,
-                                       vec6, last_value, reward_sum));
-            HIPCHK(hipGetLastError());
-            e->last_kernel = PC_KERNEL_K9;
-            return PC_OK;
-        }
-    }
+    // ---- F32 handles.  Large batches: the BIG form, 128 / 256 envs per workgroup, every wave independent; small batches: the SMALL form, 16 or
+    // 32 envs per workgroup, hidden tiles and wall-sweep parts split over the waves
     const bool small = !interleaved && (o.form == 1 || (o.form < 0 && e->N <= PC_SPLIT_MAX_ENVS));
-    const int epw = o.epw_override >= 128 ? o.epw_override
-                                                  : ((!small && e->N <= g_rollout_epw128_max) ? 128 : 256);   // big form: envs per workgroup
-    int max_G = 0, max_nV = 0;
-    for (const TrackHdr& h : e->hdr_host) { max_G = std::max(max_G, h.G); max_nV = std::max(max_nV, h.nV); }
     // fast mode: Discrete(9), every gather table in LDS behind LDS pointers, dense observation rows (big form: each wave's output
     // tile aliases its own 32 observation rows -- dead between the policy pass's operand load and the env step's store of the
     // next observation: needs D >= 17).  A workgroup stages ONE track's tables: single-track batches, or mixed ones in which
@@ -1785,146 +1630,63 @@ static int rollout_impl(pc_env* e, int prec_request, const float* image, int A, 
     // 33 rays) and cast exactly four collision rays at the reward gate: num_rays 12 / 16 / 32 (what BASELINE's configs name).  Any
     // other count that maps onto the same slots (17 or 18 nominal rays -> 18 actual: the slots of 17; 31 -> 33 with five
     // collision rays) takes the generic mode, which reads all of that from the handle.
-    const bool fast_rays = e->n_nominal == 12 || e->n_nominal == 16 || e->n_nominal == 32;
-    const bool fast_shape = A == 9 && fast_rays && e->D >= 17 && e->D <= 40 && max_G <= TAB_MAX_GATES && o.fast;
+    const bool fast_shape = A == 9 && (rays12 || rays16 || rays32) && e->D >= 17 && e->D <= 40 && f.max_G <= TAB_MAX_GATES && o.fast;
     // (the float64 refinement gathers the chain from LDS: at most FT_VTX_MAX vertices; a shape whose fast-mode tables do not fit
     // beside the weight image -- the fp32 image at 33 rays -- takes the generic mode)
     const size_t lds_fast_big = (size_t)k9_fast_lds_floats(img, 32, e->D, KS != 10, 0) * sizeof(float);   // (33 rays: one turn of the float64 lattice)
-    const bool fast = !small && fast_shape && max_nV <= FT_VTX_MAX && (!e->track_id || e->track_block >= epw) && lds_fast_big <= 160 * 1024;
+    const bool fast = !small && fast_shape && f.max_nV <= FT_VTX_MAX && (!e->track_id || e->track_block >= epw) && lds_fast_big <= 160 * 1024;
     const size_t lds_big = fast ? lds_fast_big : (size_t)(img + 256 * (4 * KS + 1) + 256 + TAB_FLOATS) * sizeof(float);
     const size_t lds_fast_small = (size_t)(img + 8 * 32 * 17 + 32 * 40 + 32 + 128 + ft_floats(true, true)) * sizeof(float);
-    const bool fast_small = small && fast_shape && max_nV <= FT_VTX_MAX && lds_fast_small <= 160 * 1024;     // (a small-form workgroup is 16 or 32 envs)
+    const bool fast_small = small && fast_shape && f.max_nV <= FT_VTX_MAX && lds_fast_small <= 160 * 1024;     // (a small-form workgroup is 16 or 32 envs)
     const size_t lds_small = fast_small ? lds_fast_small : (size_t)(img + 8 * 32 * 17 + 32 * (4 * KS + 1) + 32 + 128 + TAB_FLOATS) * sizeof(float);
-    size_t lds = small ? lds_small : lds_big;
-    if (lds > 160 * 1024) return PC_ERR_UNSUPPORTED;
+    p.lds = small ? lds_small : lds_big;
+    if (p.lds > 160 * 1024) return PC_ERR_UNSUPPORTED;
     // the track's 1/den table rides along in LDS when it fits (big_track: 361 x 28 floats = 40 KB); else the sweep forms
     // den and its reciprocal itself -- same bits either way.  Mixed batches: in the fast modes only (room for the largest track).
     // (the big form at 33 rays has 4 KB left: no closed track's table fits, so that shape is built without the table mode)
-    int rden_lds = 361 * max_nV;
-    bool all_rden = true;
-    for (const TrackHdr& h : e->hdr_host) all_rden = all_rden && h.rden_off >= 0;
-    if (!all_rden || o.rden == 0 || (e->track_id && !(small ? fast_small : fast)) || lds + (size_t)rden_lds * sizeof(float) > 160 * 1024 ||
+    p.rden_lds = 361 * f.max_nV;
+    if (!f.rden || o.rden == 0 || (e->track_id && !(small ? fast_small : fast)) || p.lds + (size_t)p.rden_lds * sizeof(float) > 160 * 1024 ||
         (!small && KS == 10))
-        rden_lds = 0;
-    lds += (size_t)rden_lds * sizeof(float);
-    const int rpl = small ? (e->R + 3) / 4 : (e->R + 1) / 2;  // 4 (x 4 sweep parts) or 2 lanes per env
+        p.rden_lds = 0;
+    p.lds += (size_t)p.rden_lds * sizeof(float);
+    const int mode = (fast || fast_small) ? (p.rden_lds ? 2 : 1) : 0;
+    if (!small) {
+        const int rpl = (e->R + 1) / 2;       // 2 lanes per env
+        if (KS == 5 && rpl == 6) {           // 12 rays, D = 18
+            PC_FULL(p.launch = prec == 2 ? roll_big_mode<5, 6, 2>(mode) : prec ? roll_big_mode<5, 6, 1>(mode) : roll_big_mode<5, 6, 0>(mode));
+        } else if (KS == 6 && rpl == 9) {    // 16 -> 17 rays, D = 23; fp16 x 2: the chain-of-28 and chain-packed kernels
+            if (prec == 2 && mode == 2 && all_nv28) PC_DEV(0, p.launch = (roll_big<6, 9, 2, 3>));
+            else if (prec == 2 && mode == 2 && all_loops) PC_FULL(p.launch = (roll_big<6, 9, 2, 5>));
+            else if (prec == 2 && mode == 1 && all_nv28) PC_FULL(p.launch = (roll_big<6, 9, 2, 4>));
+            else PC_FULL(p.launch = prec == 2 ? roll_big_mode<6, 9, 2>(mode) : prec ? roll_big_mode<6, 9, 1>(mode) : roll_big_mode<6, 9, 0>(mode));
+        } else if (KS == 10 && rpl == 17 && prec) {     // 32 -> 33 rays, D = 39
+            // (the chain-of-28 variant spills: not built.  The GENERIC mode at 33 rays -- a mixed-track batch whose workgroups straddle
+            // tracks, fast mode switched off -- spilled 100+ registers beside the split operands' policy state: not built either; that
+            // shape is PC_ERR_UNSUPPORTED here and runs through the per-step kernels, bit-identical by construction)
+            if (!mode) return PC_ERR_UNSUPPORTED;
+            if (prec == 2) PC_DEV(2, p.launch = (roll_big<10, 17, 2, 1>)); else PC_FULL(p.launch = (roll_big<10, 17, 1, 1>));
+        } else return PC_ERR_UNSUPPORTED;
+        p.kernel = PC_KERNEL_K9;
+        return PC_OK;
+    }
     // small form: 16 envs per workgroup up to 4096 envs (<= 256 workgroups: one per CU), else 32
     const int epw_small = (o.epw_override == 16 || o.epw_override == 32) ? o.epw_override
                           : ((fast_small && prec != 0 && e->R <= 17 && e->N <= 4096) ? 16 : 32);
-    if (small && epw_small == 16 && !(fast_small && prec != 0 && e->R <= 17)) return PC_ERR_UNSUPPORTED;
-    const int blocks = (int)(small ? (e->N + epw_small - 1) / epw_small : (e->N + epw - 1) / epw);
-    // 16-byte stores of the waves' 32-row blocks: the rows' offsets inside the buffers AND the buffers themselves are aligned
-    const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
-    const int mode = (fast || fast_small) ? (rden_lds ? 2 : 1) : 0;
-    bool all_nv28 = o.nv28 != 0;
-    bool all_loops = o.nv28 != 0;       // ... or every track is two equal chains of 13 or of 9 vertices (track.json: 8 walls per loop): the mixed form of those kernels
-    for (const TrackHdr& h : e->hdr_host) {
-        all_nv28 = all_nv28 && h.nV == 28 && h.n_chain == 26 && h.brk2 == 13 && h.vtxp_off >= 0;   // big_track's layout: two loops of 12 walls
-        all_loops = all_loops && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    EnvParams<float> prm = e->params<float>();
-    prm.lg = small ? 2 : 1;
-    // ---- the 16-envs-per-wave form (rollout_kernel<6, 5, 2, MD, LIT, 2>): 17 rays, fp16 x 2, the chain-packed sweeps' track layouts, the
-    // 1/den table in LDS; automatic between PC_SPLIT_MAX_ENVS and PC_MEDIUM_MAX_ENVS envs, PC_OPT_ROLLOUT_FORM = 4 at any size
-    {
-        const bool want = o.form == 4 || (o.form < 0 && o.epw_override == 0 && e->N > PC_SPLIT_MAX_ENVS && e->N <= PC_MEDIUM_MAX_ENVS);
-        const int rden_m = 361 * max_nV;
-        const size_t lds_m = (size_t)k9_fast_lds_floats(img, 16, e->D, true, rden_m) * sizeof(float);
-        if (want && KS == 6 && prec == 2 && e->n_nominal == 16 && fast_shape && o.rden != 0 && max_nV <= FT_VTX_MAX && (all_nv28 || all_loops) &&
-            (!e->track_id || e->track_block >= 128) && lds_m <= 160 * 1024) {
-            const int blocks_m = (int)((e->N + 127) / 128);
-            prm.lg = 2;
-#define PC_ROLL_MED(MD)                                                                                                  \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<6, 5, 2, MD, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_kernel<6, 5, 2, MD, false, 2>), dim3(blocks_m), dim3(512), lds_m, st, prm, image, A, (int)T, reward_scale, seed, \
-                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,  \
-                           next_term, next_trunc, rden_m, 128, vec_ok, last_value, reward_sum);                          \
-    } while (0)
-            if (all_nv28) PC_DEV(7, PC_ROLL_MED(3)); else PC_FULL(PC_ROLL_MED(5));
-#undef PC_ROLL_MED
-            HIPCHK(hipGetLastError());
-            e->last_kernel = PC_KERNEL_K9M;
-            return PC_OK;
-        }
-    }
-#define PC_ROLL_M(KSV, RPLV, PRC, MD)                                                                                    \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_kernel<KSV, RPLV, PRC, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_kernel<KSV, RPLV, PRC, MD>), dim3(blocks), dim3(512), lds, st, prm, image, A, (int)T, reward_scale, seed, \
-                           offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,  \
-                           next_term, next_trunc, rden_lds, epw, vec_ok, last_value, reward_sum);                        \
-    } while (0)
-#define PC_ROLL(KSV, RPLV, PRC)                                                                                          \
-    do {                                                                                                                 \
-        if constexpr (PRC == 2 && KSV == 6) {   /* (17 rays, default arithmetic only: the chain-of-28 kernels) */        \
-            if (mode == 2 && all_nv28) { PC_DEV(0, PC_ROLL_M(KSV, RPLV, PRC, 3)); break; }                               \
-            if (mode == 2 && all_loops) { PC_FULL(PC_ROLL_M(KSV, RPLV, PRC, 5)); break; }                                \
-            if (mode == 1 && all_nv28) { PC_FULL(PC_ROLL_M(KSV, RPLV, PRC, 4)); break; }                                 \
-        }                                                                                                                \
-        if (mode == 2) PC_FULL(PC_ROLL_M(KSV, RPLV, PRC, 2));                                                            \
-        else if (mode == 1) PC_FULL(PC_ROLL_M(KSV, RPLV, PRC, 1));                                                       \
-        else PC_FULL(PC_ROLL_M(KSV, RPLV, PRC, 0));                                                                      \
-    } while (0)
-#define PC_ROLLS_M(KSV, RPLV, PRC, MD, EPWV)                                                                             \
-    do {                                                                                                                 \
-        static bool attr_set[64] = {false};                                                                              \
-        if (e->device >= 64 || !attr_set[e->device]) {                                                                    \
-            HIPCHK(hipFuncSetAttribute((const void*)rollout_small_kernel<KSV, RPLV, PRC, MD, EPWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            if (e->device < 64) attr_set[e->device] = true;                                                                                \
-        }                                                                                                                \
-        hipLaunchKernelGGL((rollout_small_kernel<KSV, RPLV, PRC, MD, EPWV>), dim3(blocks), dim3(512), lds, st, prm, image, A, (int)T, reward_scale, \
-                           seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs, \
-                           next_term, next_trunc, rden_lds, vec_ok, last_value, reward_sum);                                     \
-    } while (0)
-#define PC_ROLLS(KSV, RPLV, PRC)                                                                                         \
-    do {                                                                                                                 \
-        if constexpr (PRC != 0 && RPLV <= 5) {                                                                           \
-            if (mode && epw_small == 16) {                                                                               \
-                if constexpr (PRC == 2 && KSV == 6) {   /* (configs[1]'s kernel: with the 1/den table in LDS the env step is compiled for it) */ \
-                    if (rden_lds) PC_DEV(1, PC_ROLLS_M(KSV, RPLV, PRC, 2, 16)); else PC_FULL(PC_ROLLS_M(KSV, RPLV, PRC, 1, 16));    \
-                } else PC_FULL(PC_ROLLS_M(KSV, RPLV, PRC, 1, 16));                                                               \
-                break;                                                                                                           \
-            }                                                                                                                    \
-        }                                                                                                                \
-        if (mode) PC_FULL(PC_ROLLS_M(KSV, RPLV, PRC, 1, 32));    /* (the small form takes the 1/den table as a run-time branch) */   \
-        else PC_FULL(PC_ROLLS_M(KSV, RPLV, PRC, 0, 32));                                                                 \
-    } while (0)
-    if (small) {
-        if (KS == 5 && rpl == 3) { PC_FULL(if (prec == 2) PC_ROLLS(5, 3, 2); else if (prec) PC_ROLLS(5, 3, 1); else PC_ROLLS(5, 3, 0)); }        // 12 rays
-        else if (KS == 6 && rpl == 5) { if (prec == 2) PC_ROLLS(6, 5, 2); else PC_FULL(if (prec) PC_ROLLS(6, 5, 1); else PC_ROLLS(6, 5, 0)); }   // 16 -> 17 rays
-        else if (KS == 10 && rpl == 9) {                                                                                                      // 32 -> 33 rays
-            PC_FULL(if (prec == 2) PC_ROLLS(10, 9, 2);
-                    else if (prec) { if (mode) PC_ROLLS_M(10, 9, 1, 1, 32); else return PC_ERR_UNSUPPORTED; }   // (bf16 x 3 in the generic mode spilled: the caller's per-step kernels take that shape)
-                    else PC_ROLLS(10, 9, 0));
-        }
-        else return PC_ERR_UNSUPPORTED;
-    } else if (KS == 5 && rpl == 6) { PC_FULL(if (prec == 2) PC_ROLL(5, 6, 2); else if (prec) PC_ROLL(5, 6, 1); else PC_ROLL(5, 6, 0)); }       // 12 rays, D = 18
-    else if (KS == 6 && rpl == 9) { if (prec == 2) PC_ROLL(6, 9, 2); else PC_FULL(if (prec) PC_ROLL(6, 9, 1); else PC_ROLL(6, 9, 0)); }          // 16 -> 17 rays, D = 23
-    else if (KS == 10 && rpl == 17 && prec) {                                                                                             // 32 -> 33 rays, D = 39
-        // (the chain-of-28 variant spills: not built.  The GENERIC mode at 33 rays -- a mixed-track batch whose workgroups straddle
-        // tracks, fast mode switched off -- spilled 100+ registers beside the split operands' policy state: not built either; that
-        // shape is PC_ERR_UNSUPPORTED here and runs through the per-step kernels, bit-identical by construction)
-        if (!mode) return PC_ERR_UNSUPPORTED;
-        if (prec == 2) PC_DEV(2, PC_ROLL_M(10, 17, 2, 1));
-        else PC_FULL(PC_ROLL_M(10, 17, 1, 1));
-    }
-    else return PC_ERR_UNSUPPORTED;
-#undef PC_ROLL_M
-#undef PC_ROLLS_M
-#undef PC_ROLLS
-#undef PC_ROLL
-    HIPCHK(hipGetLastError());
-    e->last_kernel = small ? PC_KERNEL_K9S : PC_KERNEL_K9;
+    if (epw_small == 16 && !(fast_small && prec != 0 && e->R <= 17)) return PC_ERR_UNSUPPORTED;
+    const bool epw16 = mode && epw_small == 16;
+    const int rpl = (e->R + 3) / 4;           // 4 lanes per env (x 4 sweep parts)
+    if (KS == 5 && rpl == 3) {               // 12 rays
+        PC_FULL(p.launch = prec == 2 ? roll_small_mode<5, 3, 2>(mode, epw16) : prec ? roll_small_mode<5, 3, 1>(mode, epw16) : roll_small_mode<5, 3, 0>(mode, epw16));
+    } else if (KS == 6 && rpl == 5) {        // 16 -> 17 rays (configs[1]'s kernel: with the 1/den table in LDS the env step is compiled for it)
+        if (prec == 2 && epw16 && p.rden_lds) PC_DEV(1, p.launch = (roll_small<6, 5, 2, 2, 16>));
+        else PC_FULL(p.launch = prec == 2 ? roll_small_mode<6, 5, 2>(mode, epw16) : prec ? roll_small_mode<6, 5, 1>(mode, epw16) : roll_small_mode<6, 5, 0>(mode, epw16));
+    } else if (KS == 10 && rpl == 9) {       // 32 -> 33 rays
+        if (prec == 1 && !mode) return PC_ERR_UNSUPPORTED;    // (bf16 x 3 in the generic mode spilled: the caller's per-step kernels take that shape)
+        PC_FULL(p.launch = prec == 2 ? roll_small_mode<10, 9, 2>(mode, false) : prec ? roll_small<10, 9, 1, 1, 32> : roll_small_mode<10, 9, 0>(mode, false));
+    } else return PC_ERR_UNSUPPORTED;
+    p.blocks = (int)((e->N + epw_small - 1) / epw_small);
+    p.lg = 2;
+    p.kernel = PC_KERNEL_K9S;
     return PC_OK;
 }
 
@@ -1935,8 +1697,22 @@ int pc_rollout(pc_env* e, const pc_policy* p, const float* image, int64_t T, dou
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!e || !p) return PC_ERR_INVALID_ARG;
     if (p->D != e->D || p->device != e->device) return PC_ERR_INVALID_ARG;     // the policy was built for another observation width / device
-    return rollout_impl(e, p->precision, image, p->A, T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf,
-                        trunc_buf, logprob_buf, next_obs, next_term, next_trunc, last_value, reward_sum, stream);
+    if (!image || !obs_buf || !act_buf || !rew_buf || !val_buf || !term_buf || !trunc_buf || !logprob_buf || !next_obs || !next_term || !next_trunc ||
+        T < 1 || T > (1 << 24))
+        return PC_ERR_INVALID_ARG;
+    // 16-byte stores of the waves' 32-row blocks: the rows' offsets inside the buffers AND the buffers themselves are aligned
+    const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
+    RolloutPlan plan;
+    int rc = plan_rollout(e, policy_prec(p->precision, e->D, p->A), p->A, vec_ok, plan);
+    if (rc != PC_OK) return rc;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const RolloutIO io{image, p->A, (int)T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf,
+                       next_obs, next_term, next_trunc, last_value, reward_sum};
+    rc = plan.launch(e, plan, io, (hipStream_t)stream);
+    if (rc != PC_OK) return rc;
+    e->last_kernel = plan.kernel;
+    return PC_OK;
 }
 
 int64_t pc_ppo_workspace_floats(int B, int D, int H, int A) {
