@@ -198,6 +198,27 @@ int pc_gae_episodes(int device, const float* rew, const float* val, const float*
                     const float* last_val, const float* last_term, const float* last_trunc, double gamma, double lam,
                     int64_t T, int64_t N, float* adv, float* ret, double reward_scale, double* carry, double* out, void* stream);
 
+/* ---- truncation bootstrap (Pardo et al., "Time Limits in Reinforcement Learning", 2018): pc_gae with V(final observation) in place of
+ * the next row's value at a time-limit truncation.  The reference bootstraps a truncated step t from val[t + 1] (buffer.py:53-61), but
+ * gymnasium's same-step auto-reset has already put the reset observation in row t + 1: that value is V(start line).
+ * Slots: CarEnv truncates at time >= PC_TIME_LIMIT (car_env.py:749) and any done restarts the env's time at 0, so two truncations of
+ * one env are at least PC_TIME_LIMIT steps apart; the truncation of env n at rollout step t goes to slot t / PC_TIME_LIMIT, and a
+ * rollout of T steps needs slots >= ceil(T / PC_TIME_LIMIT).
+ *   final_val [slots][N] float32 (device): V(final observation) of env n's truncation in slot k; its values are USED only at
+ *             truncated steps (trunc[t + 1][n] != 0 for t < T - 1, last_trunc[n] != 0 for t = T - 1): the other entries may hold
+ *             anything, finite or not (the kernel loads them next to the rows, every entry of the [slots][N] array must be readable).
+ * Per step, in the reference's float32 operation order:
+ *   next_v   = truncated(t) ? final_val[t / PC_TIME_LIMIT][n] : (t == T - 1 ? last_val[n] : val[t + 1][n])
+ *   delta    = (rew[t] + (gamma * next_v) * term_mask) - val[t]
+ *   last_gae = delta + (((gamma * lam) * term_mask) * trunc_mask) * last_gae     (the trace is still cut at the truncation)
+ * With final_val equal to the next-row values the result is pc_gae's, bit for bit.  carry / out: NULL (both) = no episode statistics;
+ * else pc_gae_episodes' arrays, accumulated by the same launch (the same statistics bits).  Every argument is checked before any
+ * device call; slots < ceil(T / PC_TIME_LIMIT) is PC_ERR_INVALID_ARG. */
+#define PC_TIME_LIMIT 1000
+int pc_gae_bootstrap(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
+                     const float* last_term, const float* last_trunc, const float* final_val, int64_t slots, double gamma, double lam,
+                     int64_t T, int64_t N, float* adv, float* ret, double reward_scale, double* carry, double* out, void* stream);
+
 /* ---- Agent.get_action_and_value's sampling tail (model.py:35-40): for logits [N][A] float32
  * draw action ~ Categorical(logits) and return log_prob(action) and (optionally) the entropy.
  * Counter-based RNG (Philox-4x32-10) keyed by (seed, offset): the same (seed, offset, N, A)
@@ -294,6 +315,16 @@ int pc_rollout(pc_env* e, const pc_policy* p, const float* image, int64_t T, dou
                const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
                float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
                float* reward_sum, void* stream);
+/* pc_rollout that also keeps the observation every time-limit truncation replaced (gymnasium's info["final_observation"]; the
+ * rollout buffer holds only the reset observation there): final_obs [slots][N][D] float32 (device), the truncation of env n at
+ * rollout step t in row [t / PC_TIME_LIMIT][n] (see pc_gae_bootstrap for why the slots never collide).  Only those rows are written;
+ * every other entry keeps what it held (the caller zeroes the buffer once, so a value pass never sees garbage).  Every other output
+ * is pc_rollout's, bit for bit: pc_rollout is this call with final_obs = NULL.  PC_ERR_INVALID_ARG: final_obs NULL or
+ * slots < ceil(T / PC_TIME_LIMIT). */
+int pc_rollout_final_obs(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed,
+                         uint64_t offset, const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf,
+                         float* term_buf, float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc,
+                         float* last_value, float* reward_sum, float* final_obs, int64_t slots, void* stream);
 
 /* ---- the non-GEMM work of one PPO minibatch step (train.py:230-261), three launches:
  * pc_ppo_gather : traj_*[batch_indices] (train.py:233-238,249): idx [B] int64 into the flattened trajectories

@@ -17,6 +17,7 @@ PC_ERR_INVALID_ARG, PC_ERR_IO, PC_ERR_PARSE, PC_ERR_HIP, PC_ERR_UNSUPPORTED, PC_
 PC_XCHG_HANDLE_BYTES = 128
 PC_DTYPE_F32, PC_DTYPE_F64 = 0, 1
 PC_EPISODE_BUFFER, PC_EPISODE_STEPS = 0, 1
+PC_TIME_LIMIT = 1000     # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
 PC_OPT_ROLLOUT_FORM, PC_OPT_ROLLOUT_EPW, PC_OPT_ROLLOUT_FAST = 1, 2, 3
 PC_KERNEL_NAMES = {0: "none", 1: "K9", 2: "K9s", 3: "K9-literal", 4: "K9d-filter", 5: "K9s-literal", 6: "K9d-selector", 7: "K9m", 8: "K9m-literal"}     # pc_env_last_rollout_kernel
 PC_STEP_NAMES = {0: "none", 1: "K1", 2: "K1f", 3: "K1f-table"}     # pc_env_last_step_kernel
@@ -81,6 +82,7 @@ _sig = {
     "pc_gae": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _vp]),
     "pc_episode_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp, _vp]),
     "pc_gae_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
+    "pc_gae_bootstrap": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_sample": (_i, [_i, _vp, _i64, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
     "pc_policy_create": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pc_policy_destroy": (None, [_vp]),
@@ -89,6 +91,7 @@ _sig = {
     "pc_policy_pack_checked": (_i, [_vp] + [_vp] * 8 + [_vp, _vp, _vp]),
     "pc_policy_act": (_i, [_vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _vp] + [_vp] * 5 + [_vp]),
     "pc_rollout": (_i, [_vp, _vp, _vp, _i64, _d, C.c_uint64, C.c_uint64, _vp] + [_vp] * 12 + [_vp]),
+    "pc_rollout_final_obs": (_i, [_vp, _vp, _vp, _i64, _d, C.c_uint64, C.c_uint64, _vp] + [_vp] * 12 + [_vp, _i64, _vp]),
     "pc_env_set_option": (_i, [_vp, _i, _i]),
     "pc_env_get_option": (_i, [_vp, _i, C.POINTER(_i)]),
     "pc_ppo_gather": (_i, [_i, _vp, _i, _i] + [_vp] * 10 + [_vp]),

@@ -3,7 +3,7 @@ calculate_advantages(), get().  Storage is torch tensors on the GPU; the GAE(lam
 HIP kernel behind pc_gae (bit-exact with the reference's torch expression, buffer.py:51-63)."""
 import torch
 
-from ._capi import check, lib
+from ._capi import PC_TIME_LIMIT, check, lib
 
 
 class Buffer:
@@ -39,10 +39,28 @@ class Buffer:
         return (self.obs_buf[t], self.act_buf[t], self.rew_buf[t], self.val_buf[t], self.term_buf[t], self.trunc_buf[t],
                 self.logprob_buf[t])
 
-    def calculate_advantages(self, last_vals, last_terminateds, last_truncateds, episodes=None):
+    @property
+    def final_slots(self):
+        """K = ceil(T / PC_TIME_LIMIT): an env truncates at most once per PC_TIME_LIMIT steps, its truncation at step t goes to slot
+        t // PC_TIME_LIMIT (include/ppocar.h, pc_gae_bootstrap)."""
+        return -(-self.capacity // PC_TIME_LIMIT)
+
+    def final_buffers(self):
+        """(final_obs_buf [K][N][D], final_val_buf [K][N]): the observations that time-limit truncations replaced with the reset
+        observation, and their values.  Allocated on first use, zeroed once (a slot no truncation wrote holds a finite value); their
+        addresses stay fixed (HIP-graph consumers).  Only the entries of this rollout's truncations are meaningful."""
+        if getattr(self, "final_obs_buf", None) is None:
+            K, N = self.final_slots, self.num_envs
+            self.final_obs_buf = torch.zeros((K, N, *self.obs_buf.shape[2:]), dtype=torch.float32, device=self.device)
+            self.final_val_buf = torch.zeros((K, N), dtype=torch.float32, device=self.device)
+        return self.final_obs_buf, self.final_val_buf
+
+    def calculate_advantages(self, last_vals, last_terminateds, last_truncateds, episodes=None, final_values=None):
         """buffer.py:36-64: GAE(lambda) with separate terminated / truncated masks -> (adv_buf, ret_buf).
         episodes: an EpisodeStats (ppo-car_amd/episodes.py) -- its carry and out are updated from the same rows by the same
-        launch (pc_gae_episodes: the same adv / ret bits as pc_gae)."""
+        launch (pc_gae_episodes: the same adv / ret bits as pc_gae).
+        final_values: [K][N] float32 (final_val_buf) -- a truncated step bootstraps from V(final observation) instead of the
+        reset observation's value in the next row (pc_gae_bootstrap; episodes combine with it in the same launch)."""
         assert self.ptr == self.capacity, "Buffer not full"
         if self.device.type != "cuda":
             raise RuntimeError("Buffer.calculate_advantages runs the HIP GAE kernel: the buffer must live on the GPU")
@@ -56,6 +74,18 @@ class Buffer:
         adv, ret = self.adv_buf, self.ret_buf
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if final_values is not None:
+            fv = final_values.detach()
+            assert fv.dtype == torch.float32 and fv.is_contiguous() and fv.device == self.device and fv.dim() == 2 and fv.shape[1] == N
+            carry = out = None
+            if episodes is not None:
+                assert episodes.num_envs == N and episodes.device == torch.device("cuda", dev)
+                carry, out = episodes.carry.data_ptr(), episodes.out.data_ptr()
+            check(lib.pc_gae_bootstrap(dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(),
+                                       self.trunc_buf.data_ptr(), lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), fv.data_ptr(), fv.shape[0],
+                                       float(self.gamma), float(self.gae_lambda), T, N, adv.data_ptr(), ret.data_ptr(),
+                                       episodes.reward_scaling if episodes is not None else 1.0, carry, out, stream), "pc_gae_bootstrap")
+            return adv, ret
         if episodes is not None:
             assert episodes.num_envs == N and episodes.device == torch.device("cuda", dev)
             check(lib.pc_gae_episodes(dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(),

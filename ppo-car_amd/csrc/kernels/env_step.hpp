@@ -421,7 +421,8 @@ __device__ __forceinline__ void wall_sweep_loops(const VtxP* vp, const float pxr
 
 // One CarEnv.step (car_env.py:693-760) + TransformReward + same-step auto-reset for the env whose state the
 // 2^lg lanes of this group hold in `st` (updated in place, identically in every lane).  Lane g sweeps rays
-// g, g + G, ...  Observation entries go to orow (global row), frow (pre-reset obs, optional) and lrow (an LDS
+// g, g + G, ...  Observation entries go to orow (global row), frow (pre-reset obs, optional; with frow_trunc only where the step
+// truncated: the persistent rollouts' final-observation capture) and lrow (an LDS
 // copy for the persistent rollout kernel, optional).  The per-env scalars come back in registers.
 // SEL (T = double, the per-step kernel): on a track inside the selector's limits (TrackHdr::sel_ok) the walls are not tested pair by
 // pair: the float32 sweep selects each ray's wall and the literal arithmetic measures it (lit_fast / lit_careful, env_math.hpp) --
@@ -432,7 +433,8 @@ template <typename T, int RPL, int PARTS = 1, bool TAB = false, bool TWOPASS = f
 __device__ __forceinline__ void env_step_core(const EnvParams<T>& p, const int trk, const int g, const int lg, EnvRegs& st,
                                               const int64_t a, const double reward_scale, float* __restrict__ orow,
                                               float* __restrict__ frow, float* lrow, float& reward_f, bool& term, bool& trunc,
-                                              int& passed_out, const int part = 0, float* exch = nullptr, lds_cfp rdl = nullptr) {
+                                              int& passed_out, const int part = 0, float* exch = nullptr, lds_cfp rdl = nullptr,
+                                              const bool frow_trunc = false) {
     // TAB (persistent kernels, when the track's 1/den table fits LDS): `rdl` = this track's [361][nV] table in LDS; the sweep
     // reads 1/den instead of forming den and its reciprocal (9 quarter-rate v_rcp_f32 per vertex otherwise) -- the table
     // holds exactly the bits the arithmetic path produces, so both paths are interchangeable.
@@ -833,7 +835,7 @@ __device__ __forceinline__ void env_step_core(const EnvParams<T>& p, const int t
             const float o = done ? robs[6 + ray] : v;
             orow[6 + ray] = o;
             if (lrow) lrow[6 + ray] = o;
-            if (frow) frow[6 + ray] = v;
+            if (frow && (!frow_trunc || trunc)) frow[6 + ray] = v;
         }
     }
     if (g == 0 && store && orow) {
@@ -849,7 +851,7 @@ __device__ __forceinline__ void env_step_core(const EnvParams<T>& p, const int t
             const float o = done ? robs[i] : hd[i];
             orow[i] = o;
             if (lrow) lrow[i] = o;
-            if (frow) frow[i] = hd[i];
+            if (frow && (!frow_trunc || trunc)) frow[i] = hd[i];
         }
     }
     // ---- new state (every lane of the group keeps the same copy)

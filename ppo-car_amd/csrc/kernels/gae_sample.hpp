@@ -230,6 +230,91 @@ __global__ __launch_bounds__(256) void gae_episode_kernel(const float* __restric
     acc.finish(carry, out, e, N);
 }
 
+// K3b: K3 with the truncation bootstrap (pc_gae_bootstrap).  At a truncated step t -- the trunc flag in row t + 1, or last_trunc for
+// t = T - 1 -- next_val is V(final observation) from final_val[t / PC_TIME_LIMIT] instead of val[t + 1] / last_val (which gymnasium's
+// same-step auto-reset made V(reset observation)); every float32 operation and its order stay K3's, and so does the trace cut
+// (trunc_mask).  final_val's values are used only at truncated steps.  Each block of U rows loads the (at most two) slots its steps
+// lie in together with its rows: a load per truncation inside the recurrence made every wave wait for its outstanding stores
+// (1.31 x K3); these are two coalesced L2-resident words per env and block, issued with the rows.  EPI: K3e's episode statistics
+// on the same rows (EpisodeAcc, the same steps in the same order: pc_gae_episodes' bits).
+template <bool EPI>
+__global__ __launch_bounds__(256) void gae_bootstrap_kernel(const float* __restrict__ rew, const float* __restrict__ val,
+                                                            const float* __restrict__ term, const float* __restrict__ trunc,
+                                                            const float* __restrict__ last_val, const float* __restrict__ last_term,
+                                                            const float* __restrict__ last_trunc, const float* __restrict__ final_val,
+                                                            const float g, const float gl, const int64_t T, const int64_t N,
+                                                            float* __restrict__ adv, float* __restrict__ ret, const double inv_s,
+                                                            double* __restrict__ carry, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const float lt = last_term[e], ltr = last_trunc[e];
+    float next_val = ltr != 0.0f ? final_val[(T - 1) / PC_TIME_LIMIT * N + e] : last_val[e];
+    float tmask = 1.0f - lt;
+    float trmask = 1.0f - ltr;
+    bool done = (lt != 0.0f) | (ltr != 0.0f);
+    float last_gae = 0.0f;
+    EpisodeAcc acc;
+    constexpr int U = 8;
+    int64_t t = T - 1;
+    for (; t >= U - 1; t -= U) {
+        float r[U], v[U], tm[U], tr[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int64_t off = (t - j) * N + e;
+            r[j] = rew[off];
+            v[j] = val[off];
+            tm[j] = term[off];
+            tr[j] = trunc[off];
+        }
+        // steps t - 1 .. t - U: slot sa from step sb on, slot sa - 1 (or sa) below it
+        const int64_t sa = (t - 1) / PC_TIME_LIMIT, sb = sa * PC_TIME_LIMIT;
+        const float fa = final_val[sa * N + e];
+        const float fb = final_val[(t - U > 0 ? t - U : 0) / PC_TIME_LIMIT * N + e];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int64_t off = (t - j) * N + e;
+            float tmp = g * next_val;
+            tmp = tmp * tmask;
+            float delta = r[j] + tmp;
+            delta = delta - v[j];
+            float c = gl * tmask;
+            c = c * trmask;
+            c = c * last_gae;
+            last_gae = delta + c;
+            adv[off] = last_gae;
+            ret[off] = last_gae + v[j];
+            if constexpr (EPI) acc.step(r[j], done, inv_s);
+            // row t - j holds the flags of step t - j - 1: a truncation there bootstraps from its final observation
+            const int64_t s = t - j - 1;
+            next_val = (tr[j] != 0.0f && s >= 0) ? (s >= sb ? fa : fb) : v[j];
+            tmask = 1.0f - tm[j];
+            trmask = 1.0f - tr[j];
+            if constexpr (EPI) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
+        }
+    }
+    for (; t >= 0; --t) {
+        const int64_t off = t * N + e;
+        const float r = rew[off], v = val[off];
+        float tmp = g * next_val;
+        tmp = tmp * tmask;
+        float delta = r + tmp;
+        delta = delta - v;
+        float c = gl * tmask;
+        c = c * trmask;
+        c = c * last_gae;
+        last_gae = delta + c;
+        adv[off] = last_gae;
+        ret[off] = last_gae + v;
+        if constexpr (EPI) acc.step(r, done, inv_s);
+        const float tmf = term[off], trf = trunc[off];
+        next_val = (trf != 0.0f && t >= 1) ? final_val[(t - 1) / PC_TIME_LIMIT * N + e] : v;
+        tmask = 1.0f - tmf;
+        trmask = 1.0f - trf;
+        if constexpr (EPI) done = (tmf != 0.0f) | (trf != 0.0f);
+    }
+    if constexpr (EPI) acc.finish(carry, out, e, N);
+}
+
 // K3e standalone: the same accounting without GAE.  STEPS = false: the Buffer layout (step t's flags in row t + 1, step
 // T - 1's in last_*; row 0 is never read); STEPS = true: flags[t] belong to rew[t] (pc_env_step / pc_env_step_many rows).
 template <bool STEPS>

@@ -948,7 +948,8 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
                                                       float* __restrict__ logprob_buf, float* __restrict__ next_obs,
                                                       float* __restrict__ next_term, float* __restrict__ next_trunc,
                                                       const int rden_lds, const int epw, const int vec_ok,
-                                                      float* __restrict__ last_val, float* __restrict__ rew_sum) {
+                                                      float* __restrict__ last_val, float* __restrict__ rew_sum,
+                                                      float* __restrict__ final_obs) {
     constexpr int dbg = PC_ABLATE;  // 0 in the product build (see PC_ABLATE)
     constexpr int GE = 1 << LGE, EPWV = 64 / GE;      // lanes per env, envs per wave
     constexpr int HID = 256, NT = 2 * HID / 16, LD1 = pol_ld1(KS), ET = EPWV / 16;
@@ -1256,6 +1257,19 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
                     rsum += rw;
                     PC_STAMP(6)
                     if (__builtin_amdgcn_ballot_w64(done) != 0) {   // wave-uniform: ~1.5 % of env steps end an episode
+                        // final-observation capture (pc_rollout_final_obs): a truncated env's row, before the fix-up below overwrites
+                        // the same entries from the same lanes -- rows written by the wave's other lanes: fence first (as K1f does)
+                        const bool cap = e_valid & (cf != 0.0f);
+                        if (final_obs != nullptr && __builtin_amdgcn_ballot_w64(cap) != 0) {      // (uniform; ~1 step in 1000)
+                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            if (cap) {
+                                float* fo = final_obs + ((int64_t)(t / PC_TIME_LIMIT) * N + e_env) * DC;
+#pragma unroll
+                                for (int j = 0; j < (DC + GE - 1) / GE; ++j)
+                                    if (g + GE * j < DC) fo[g + GE * j] = lrow[g + GE * j];
+                            }
+                        }
                         if (done) {
                             // the reset observation's entries f = g, g + 2, ...: all reads issued, then the writes (rolled, every
                             // entry is an LDS round trip in series -- and some env of a wave finishes in a third of the steps of a
@@ -1356,12 +1370,14 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
             __builtin_amdgcn_s_setprio(2);
             // ---------------- E(t)
             float* orow = last ? next_obs + e_env * D : obs_buf + ((int64_t)(t + 1) * N + e_env) * D;
+            // final-observation capture (pc_rollout_final_obs): the step writes the pre-reset row where it truncates
+            float* frow = final_obs ? final_obs + ((int64_t)(t / PC_TIME_LIMIT) * N + e_env) * D : nullptr;
             float rw;
             bool term, trunc;
             int passed;
             if (rden_lds)  // uniform
-                env_step_core<float, RPL, 1, true, true>(q, trk, g, 1, st, (int64_t)sAct[el], reward_scale, orow, nullptr, sObs + el * LDX, rw,
-                                                   term, trunc, passed, 0, nullptr, rdl);
+                env_step_core<float, RPL, 1, true, true>(q, trk, g, 1, st, (int64_t)sAct[el], reward_scale, orow, frow, sObs + el * LDX, rw,
+                                                   term, trunc, passed, 0, nullptr, rdl, true);
             else {
                 // The step runs once per DISTINCT TRACK ID among the wave's envs (K1's waterfall): one pass for a single-track batch and
                 // for mixed batches in blocks of 32 envs; with tracks INTERLEAVED inside the wave (car_env.py:621-628 lets every env sit
@@ -1372,8 +1388,8 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
                     const int cur = __builtin_amdgcn_readlane(trk, __builtin_ctzll(todo));
                     const bool match = trk == cur;
                     if (match)
-                        env_step_core<float, RPL, 1, false, true>(q, cur, g, 1, st, (int64_t)sAct[el], reward_scale, orow, nullptr, sObs + el * LDX, rw,
-                                                                  term, trunc, passed);
+                        env_step_core<float, RPL, 1, false, true>(q, cur, g, 1, st, (int64_t)sAct[el], reward_scale, orow, frow, sObs + el * LDX, rw,
+                                                                  term, trunc, passed, 0, nullptr, nullptr, true);
                     todo &= ~__builtin_amdgcn_ballot_w64(match);
                 } while (todo);
             }
@@ -1417,7 +1433,8 @@ __global__ __launch_bounds__(512) void rollout_f64_kernel(const EnvParams<double
                                                           float* __restrict__ term_buf, float* __restrict__ trunc_buf,
                                                           float* __restrict__ logprob_buf, float* __restrict__ next_obs,
                                                           float* __restrict__ next_term, float* __restrict__ next_trunc,
-                                                          const int epw, float* __restrict__ last_val, float* __restrict__ rew_sum) {
+                                                          const int epw, float* __restrict__ last_val, float* __restrict__ rew_sum,
+                                                          float* __restrict__ final_obs) {
     static_assert(PREC != 0, "split-operand policy forms");
     constexpr int HID = 256, NT = 2 * HID / 16, ET = 2, LDO = 20;
     constexpr int NG = pol_ng(KS), KB = pol_kb(KS);
@@ -1523,6 +1540,7 @@ __global__ __launch_bounds__(512) void rollout_f64_kernel(const EnvParams<double
         if (e_valid) {
             // ---------------- E(t): envs.step (train.py:185) in the reference's float64
             float* orow = last ? next_obs + e_env * D : obs_buf + ((int64_t)(t + 1) * N + e_env) * D;
+            float* frow = final_obs ? final_obs + ((int64_t)(t / PC_TIME_LIMIT) * N + e_env) * D : nullptr;   // (the capture: see rollout_kernel)
             float rw;
             bool term, trunc;
             int passed;
@@ -1531,8 +1549,8 @@ __global__ __launch_bounds__(512) void rollout_f64_kernel(const EnvParams<double
                 const int cur = __builtin_amdgcn_readlane(trk, __builtin_ctzll(todo));
                 const bool match = trk == cur;
                 if (match)
-                    env_step_core<double, RPL, 1, false, true, SEL ? 2 : 0>(p, cur, g, 1, st, (int64_t)act_reg, reward_scale, orow, nullptr, sObs + el * LDX, rw,
-                                                                     term, trunc, passed);
+                    env_step_core<double, RPL, 1, false, true, SEL ? 2 : 0>(p, cur, g, 1, st, (int64_t)act_reg, reward_scale, orow, frow, sObs + el * LDX, rw,
+                                                                     term, trunc, passed, 0, nullptr, nullptr, true);
                 todo &= ~__builtin_amdgcn_ballot_w64(match);
             } while (todo);
             rsum += rw;
@@ -1570,7 +1588,8 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
                                                             float* __restrict__ logprob_buf, float* __restrict__ next_obs,
                                                             float* __restrict__ next_term, float* __restrict__ next_trunc,
                                                             const int rden_lds, const int vec_ok,
-                                                            float* __restrict__ last_val, float* __restrict__ rew_sum) {
+                                                            float* __restrict__ last_val, float* __restrict__ rew_sum,
+                                                            float* __restrict__ final_obs) {
     constexpr int dbg = PC_ABLATE;  // 0 in the product build (see PC_ABLATE)
     // EPW = envs per workgroup: 32 (two groups of 4 waves = 4 sweep parts for 16 envs each; each wave 2 env tiles of the policy
     // pass) or 16 (up to 4096 envs: twice the workgroups -- all 256 CUs at BASELINE configs[1] -- and every phase of the step
@@ -1811,6 +1830,19 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
                 }
                 rsum += rw;
                 if (__builtin_amdgcn_ballot_w64(done) != 0) {
+                    // final-observation capture (pc_rollout_final_obs): the row-writing lanes copy a truncated env's row out before
+                    // the fix-up below overwrites the same entries (fence first: the row's entries come from other lanes of the wave)
+                    const bool cap = e_valid & (cf != 0.0f);
+                    if (final_obs != nullptr && __builtin_amdgcn_ballot_w64(cap) != 0) {      // (uniform; ~1 step in 1000)
+                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        if (cap && part == 0) {
+                            float* fo = final_obs + ((int64_t)(t / PC_TIME_LIMIT) * N + e_env) * DC;
+#pragma unroll
+                            for (int j = 0; j < (DC + 3) / 4; ++j)
+                                if (g + 4 * j < DC) fo[g + 4 * j] = lrow[g + 4 * j];
+                        }
+                    }
                     if (done) {
                         if (part == 0)   // (uniform) the row-writing wave: reset observation of finished envs
                         {   // all reads, then the writes (see rollout_kernel)
@@ -1879,16 +1911,18 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
         } else if constexpr (EPW == 32) {
             if (!(dbg & 2)) {
                 float* orow = !e_valid ? nullptr : (last ? next_obs + e_env * D : obs_buf + ((int64_t)(t + 1) * N + e_env) * D);
+                float* frow = (final_obs && e_valid) ? final_obs + ((int64_t)(t / PC_TIME_LIMIT) * N + e_env) * D : nullptr;   // (the capture)
                 float rw;
                 bool term, trunc;
                 int passed;
                 if (rden_lds)  // uniform
-                    env_step_core<float, RPL, PARTS, true, true>(q, trk, g, 2, st, (int64_t)sAct[el], reward_scale, orow, nullptr,
+                    env_step_core<float, RPL, PARTS, true, true>(q, trk, g, 2, st, (int64_t)sAct[el], reward_scale, orow, frow,
                                                            e_valid && part == 0 ? sObs + el * LDX : nullptr, rw, term, trunc, passed, part,
-                                                           exch, rdl);
+                                                           exch, rdl, true);
                 else
-                    env_step_core<float, RPL, PARTS, false, true>(q, trk, g, 2, st, (int64_t)sAct[el], reward_scale, orow, nullptr,
-                                                     e_valid && part == 0 ? sObs + el * LDX : nullptr, rw, term, trunc, passed, part, exch);
+                    env_step_core<float, RPL, PARTS, false, true>(q, trk, g, 2, st, (int64_t)sAct[el], reward_scale, orow, frow,
+                                                     e_valid && part == 0 ? sObs + el * LDX : nullptr, rw, term, trunc, passed, part, exch,
+                                                     nullptr, true);
                 rsum += rw;
                 if (e_valid && g == 0 && part == 0) {
                     rew_buf[(int64_t)t * N + e_env] = rw;

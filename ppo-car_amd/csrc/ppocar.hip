@@ -11,6 +11,7 @@
 //   K3  gae_kernel                      Buffer.calculate_advantages (buffer.py:36-64)
 //   K3e gae_episode_kernel / episode_kernel<STEPS>   episode return, length, gates and laps on K3's rows (pc_gae_episodes) or alone
 //                                       (pc_episode_stats)
+//   K3b gae_bootstrap_kernel<EPI>       K3 with V(final observation) at time-limit truncations (pc_gae_bootstrap; EPI: K3e's statistics too)
 //   K4  sample_kernel                   Categorical(logits).sample / log_prob / entropy (model.py:35-40)
 //   K5  policy_kernel<KS, SPLIT, PREC>  Agent.get_action_and_value(x) of the rollout (model.py:34-41): both MLPs on the
 //                                       matrix cores + the draw; policy_pack*_kernel build its LDS weight image
@@ -382,6 +383,7 @@ struct RolloutIO {
     uint64_t seed, offset;
     const uint64_t* offset_dev;
     float *obs_buf, *act_buf, *rew_buf, *val_buf, *term_buf, *trunc_buf, *logprob_buf, *next_obs, *next_term, *next_trunc, *last_value, *reward_sum;
+    float* final_obs;   // pc_rollout_final_obs's [slots][N][D] (NULL: pc_rollout)
 };
 
 // what pc_rollout launches (plan_rollout): the kernel instance, through the launcher of its family (roll_big / roll_small / roll_f64), its grid
@@ -404,7 +406,7 @@ static int roll_big(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, h
     return launch_lds<rollout_kernel<KS, RPL, PREC, MODE, LIT, LGE>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed,
                                                                       c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf, c.term_buf,
                                                                       c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.rden_lds,
-                                                                      p.epw, p.vec_ok, c.last_value, c.reward_sum);
+                                                                      p.epw, p.vec_ok, c.last_value, c.reward_sum, c.final_obs);
 }
 
 template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false>
@@ -414,7 +416,8 @@ static int roll_small(const pc_env* e, const RolloutPlan& p, const RolloutIO& c,
     return launch_lds<rollout_small_kernel<KS, RPL, PREC, MODE, EPW, LIT>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale,
                                                                             c.seed, c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf,
                                                                             c.term_buf, c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term,
-                                                                            c.next_trunc, p.rden_lds, p.vec_ok, c.last_value, c.reward_sum);
+                                                                            c.next_trunc, p.rden_lds, p.vec_ok, c.last_value, c.reward_sum,
+                                                                            c.final_obs);
 }
 
 template <int KS, int RPL, int PREC, bool SEL>
@@ -423,7 +426,8 @@ static int roll_f64(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, h
     prm.lg = p.lg;
     return launch_lds<rollout_f64_kernel<KS, RPL, PREC, SEL>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed, c.offset,
                                                                c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf, c.term_buf, c.trunc_buf,
-                                                               c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.epw, c.last_value, c.reward_sum);
+                                                               c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.epw, c.last_value, c.reward_sum,
+                                                               c.final_obs);
 }
 
 // rollout_kernel's generic mode (0) or fast mode (1; 2: with the 1/den table in LDS)
@@ -1227,6 +1231,31 @@ int pc_gae_episodes(int device, const float* rew, const float* val, const float*
     return PC_OK;
 }
 
+int pc_gae_bootstrap(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
+                     const float* last_term, const float* last_trunc, const float* final_val, int64_t slots, double gamma, double lam,
+                     int64_t T, int64_t N, float* adv, float* ret, double reward_scale, double* carry, double* out, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!rew || !val || !term || !trunc || !last_val || !last_term || !last_trunc || !final_val || !adv || !ret || T < 1 || N < 1)
+        return PC_ERR_INVALID_ARG;
+    if (slots < (T + PC_TIME_LIMIT - 1) / PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
+    const bool epi = carry != nullptr || out != nullptr;
+    if (epi && (!carry || !out)) return PC_ERR_INVALID_ARG;
+    if (epi && (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale))) return PC_ERR_INVALID_ARG;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int blocks = (int)((N + 255) / 256);
+    if (epi)
+        hipLaunchKernelGGL(gae_bootstrap_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
+                           last_term, last_trunc, final_val, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0 / reward_scale, carry, out);
+    else
+        hipLaunchKernelGGL(gae_bootstrap_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
+                           last_term, last_trunc, final_val, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
 int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, uint64_t offset, int64_t* actions,
               float* logprob, float* entropy, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
@@ -1690,11 +1719,35 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
     return PC_OK;
 }
 
+static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
+                       const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
+                       float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
+                       float* reward_sum, float* final_obs, hipStream_t stream);
+
 int pc_rollout(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
                const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
                float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
                float* reward_sum, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    return rollout_run(e, p, image, T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf,
+                       next_obs, next_term, next_trunc, last_value, reward_sum, nullptr, (hipStream_t)stream);
+}
+
+int pc_rollout_final_obs(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed,
+                         uint64_t offset, const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf,
+                         float* term_buf, float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc,
+                         float* last_value, float* reward_sum, float* final_obs, int64_t slots, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!final_obs || T < 1 || slots < (T + PC_TIME_LIMIT - 1) / PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
+    return rollout_run(e, p, image, T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf,
+                       next_obs, next_term, next_trunc, last_value, reward_sum, final_obs, (hipStream_t)stream);
+}
+
+// pc_rollout / pc_rollout_final_obs: one dispatch (plan_rollout), one launch
+static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
+                       const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
+                       float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
+                       float* reward_sum, float* final_obs, hipStream_t stream) {
     if (!e || !p) return PC_ERR_INVALID_ARG;
     if (p->D != e->D || p->device != e->device) return PC_ERR_INVALID_ARG;     // the policy was built for another observation width / device
     if (!image || !obs_buf || !act_buf || !rew_buf || !val_buf || !term_buf || !trunc_buf || !logprob_buf || !next_obs || !next_term || !next_trunc ||
@@ -1708,8 +1761,8 @@ int pc_rollout(pc_env* e, const pc_policy* p, const float* image, int64_t T, dou
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const RolloutIO io{image, p->A, (int)T, reward_scale, seed, offset, offset_dev, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf,
-                       next_obs, next_term, next_trunc, last_value, reward_sum};
-    rc = plan.launch(e, plan, io, (hipStream_t)stream);
+                       next_obs, next_term, next_trunc, last_value, reward_sum, final_obs};
+    rc = plan.launch(e, plan, io, stream);
     if (rc != PC_OK) return rc;
     e->last_kernel = plan.kernel;
     return PC_OK;

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._capi import check, lib
+from ._capi import PC_TIME_LIMIT, check, lib
 from .buffer import Buffer
 from .env import VecCarEnv
 from .episodes import EpisodeStats, episode_scalars
@@ -99,6 +99,14 @@ class PPOConfig:
     rollout_fast: int = 1                  # workgroup 0 automatic / 16 / 32 / 128 / 256; fast 1 / 2 / 0 (table-driven modes on / generic sweep / off)
     episode_stats: bool = False            # run_epoch adds charts/episodes, episodic_return (+ _min / _max), episodic_length, gates_per_episode,
                                            # laps_per_episode: taken by the GAE launch on the rows it loads anyway (pc_gae_episodes)
+    truncation_bootstrap: str = "reference"  # GAE's next value at a time-limit truncation: "reference" = val_buf[t + 1] as the reference
+                                           # (buffer.py:53-61), which gymnasium's same-step auto-reset made V(reset observation); "final_obs" =
+                                           # V(the observation the truncated step returned): the rollout keeps it in Buffer.final_obs_buf,
+                                           # one value pass per slot (bootstrap_value's arithmetic), then pc_gae_bootstrap
+
+    def __post_init__(self):
+        if self.truncation_bootstrap not in ("reference", "final_obs"):
+            raise ValueError(f"PPOConfig.truncation_bootstrap must be 'reference' or 'final_obs', not {self.truncation_bootstrap!r}")
 
 
 def flatten_parameters(module):
@@ -725,6 +733,12 @@ class Trainer:
         self.rollout_mode = None
         self.mega_events = None      # bench.py: list of (start, end) events around each pc_rollout launch
         self.episodes = EpisodeStats(N, cfg.reward_scaling, self.device) if cfg.episode_stats else None   # carry 0: the envs were just reset
+        self.final_obs = cfg.truncation_bootstrap == "final_obs"
+        if self.final_obs:      # the side buffers of one rollout, and the per-step paths' pre-reset rows (pc_env_step's final_obs)
+            self.buffer.final_buffers()
+            self._final_step = torch.zeros(N, *self.obs_dim, device=self.device)
+            self._fv_act = torch.empty(N, dtype=torch.int64, device=self.device)
+            self._fv_logprob = torch.empty(N, device=self.device)
 
     # ---- train.py:173-195 ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -751,14 +765,18 @@ class Trainer:
             last = t == T - 1
             out = (self.next_obs if last else buf.obs_buf[t + 1], buf.rew_buf[t],
                    self.next_term if last else buf.term_buf[t + 1], self.next_trunc if last else buf.trunc_buf[t + 1])
+            fo = self._final_step if self.final_obs else None
             if events and self.profile_stride and t % self.profile_stride == 0:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                envs.step(actions, out=out)
+                envs.step(actions, out=out, final_obs=fo)
                 e1.record()
                 self.k1_events.append((e0, e1))
             else:
-                envs.step(actions, out=out)          # train.py:185 -- zero-copy into the buffer rows
+                envs.step(actions, out=out, final_obs=fo)   # train.py:185 -- zero-copy into the buffer rows
+            if fo is not None:    # the truncated envs' pre-reset rows -> slot t // PC_TIME_LIMIT (no host sync: graph-capturable)
+                slot = buf.final_obs_buf[t // PC_TIME_LIMIT]
+                torch.where((out[3] != 0).unsqueeze(1), fo, slot, out=slot)
         self.rng_base += T                           # next rollout draws from fresh Philox counters
 
     @torch.no_grad()
@@ -777,15 +795,19 @@ class Trainer:
         if self._boot_val is None:
             self._boot_val = torch.empty(cfg.n_envs, device=self.device)       # the final observation's value (train.py:200)
             self._rew_sum = torch.empty(cfg.n_envs, device=self.device)        # per-env reward totals (train.py:272)
-        rc = lib.pc_rollout(self.envs._h, agent._image_handle, agent._image.data_ptr(), cfg.n_steps, float(cfg.reward_scaling),
-                              int(agent.rng_seed), 0, self.rng_base.data_ptr(), buf.obs_buf.data_ptr(), buf.act_buf.data_ptr(),
-                              buf.rew_buf.data_ptr(), buf.val_buf.data_ptr(), buf.term_buf.data_ptr(), buf.trunc_buf.data_ptr(),
-                              buf.logprob_buf.data_ptr(), self.next_obs.data_ptr(), self.next_term.data_ptr(),
-                              self.next_trunc.data_ptr(), self._boot_val.data_ptr(), self._rew_sum.data_ptr(),
-                              torch.cuda.current_stream(self.device).cuda_stream)
+        args = (self.envs._h, agent._image_handle, agent._image.data_ptr(), cfg.n_steps, float(cfg.reward_scaling),
+                int(agent.rng_seed), 0, self.rng_base.data_ptr(), buf.obs_buf.data_ptr(), buf.act_buf.data_ptr(),
+                buf.rew_buf.data_ptr(), buf.val_buf.data_ptr(), buf.term_buf.data_ptr(), buf.trunc_buf.data_ptr(),
+                buf.logprob_buf.data_ptr(), self.next_obs.data_ptr(), self.next_term.data_ptr(),
+                self.next_trunc.data_ptr(), self._boot_val.data_ptr(), self._rew_sum.data_ptr())
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.final_obs:      # the same launch, plus the truncated envs' final observations in buf.final_obs_buf
+            rc = lib.pc_rollout_final_obs(*args, buf.final_obs_buf.data_ptr(), buf.final_slots, stream)
+        else:
+            rc = lib.pc_rollout(*args, stream)
         if rc == -5:       # PC_ERR_UNSUPPORTED: shape outside the persistent kernel's menu
             return False
-        check(rc, "pc_rollout")
+        check(rc, "pc_rollout_final_obs" if self.final_obs else "pc_rollout")
         self._aux_valid = True   # the launch also delivered the bootstrap values and the reward totals of THIS rollout
         if ev is not None:
             ev[1].record()
@@ -830,6 +852,22 @@ class Trainer:
         self.buffer.ptr = cfg.n_steps
         self.global_step_idx += cfg.n_envs * cfg.n_steps * self.world_size   # train.py:174, whole job
 
+    @torch.no_grad()
+    def final_values(self):
+        """V(final observation) of every slot of buf.final_obs_buf -> buf.final_val_buf, in bootstrap_value's arithmetic: "kernel" = the
+        fused policy step, one call of N rows per slot (the handle's automatic form is the rollout's: each value is what the rollout
+        writes into val_buf for that observation), at an explicit Philox offset (the draw is discarded; agent._rng_offset and
+        rng_base do not move); "fp32" = agent.get_value.  Entries no truncation wrote are values of whatever the slot held."""
+        buf, agent = self.buffer, self.agent
+        fo, fv = buf.final_buffers()
+        for k in range(buf.final_slots):
+            if self.cfg.bootstrap_value == "kernel":
+                agent.act(fo[k], out_action=self._fv_act, out_logprob=self._fv_logprob, out_value=fv[k], fused=True, repack=False,
+                          offset=0)
+            else:
+                fv[k].copy_(agent.get_value(fo[k]).view(-1))
+        return fv
+
     # ---- train.py:197-269 ---------------------------------------------------------------------------
     def update(self):
         buf, agent = self.buffer, self.agent
@@ -839,8 +877,10 @@ class Trainer:
             next_values = (self._boot_val if in_kernel else agent.get_value(self.next_obs)).reshape(1, -1)
             if self.episodes is not None:
                 self.episodes.clear()       # this epoch's finished episodes only; the carry spans epochs
+            final_values = self.final_values() if self.final_obs else None     # (truncation_bootstrap = "final_obs")
             adv, ret = buf.calculate_advantages(next_values, self.next_term.reshape(1, -1),
-                                                self.next_trunc.reshape(1, -1), episodes=self.episodes)   # :203
+                                                self.next_trunc.reshape(1, -1), episodes=self.episodes,
+                                                final_values=final_values)   # :203
         obs, act, _val, logprob = buf.get()                                                      # :206
         self.learner.update(obs.view(-1, *self.obs_dim), act.view(-1), logprob.view(-1), adv.view(-1), ret.view(-1))
         self._aux_valid = False     # the in-kernel bootstrap values belong to THAT rollout and THOSE parameters only

@@ -55,6 +55,9 @@ def parse_args(argv=None):
                    "fetching every epoch's scalars before the next epoch is launched (the reference's order, the default: it costs ~1 %% at 65536 envs)")
     p.add_argument("--episode-stats", action="store_true", help="print and log episodic return, length, gates and laps per episode "
                    "(charts/episodes, charts/episodic_*, charts/gates_per_episode, charts/laps_per_episode)")
+    p.add_argument("--truncation-bootstrap", default="reference", choices=["reference", "final_obs"],
+                   help="GAE's next value at a time-limit truncation: the reference's val_buf[t + 1] (the reset observation's value after "
+                   "the auto-reset), or the value of the observation the truncated step returned")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -97,7 +100,7 @@ def main(argv=None):
                     reward_scaling=args.reward_scaling, track=args.track, num_rays=args.num_rays, env_dtype=args.env_dtype,
                     seed=args.seed, full_sweep=args.full_sweep, bootstrap_value=args.bootstrap_value,
                     policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range,
-                    episode_stats=args.episode_stats)
+                    episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
