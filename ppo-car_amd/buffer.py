@@ -74,29 +74,22 @@ class Buffer:
         adv, ret = self.adv_buf, self.ret_buf
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        if final_values is not None:
-            fv = final_values.detach()
-            assert fv.dtype == torch.float32 and fv.is_contiguous() and fv.device == self.device and fv.dim() == 2 and fv.shape[1] == N
-            carry = out = None
-            if episodes is not None:
-                assert episodes.num_envs == N and episodes.device == torch.device("cuda", dev)
-                carry, out = episodes.carry.data_ptr(), episodes.out.data_ptr()
-            check(lib.pc_gae_bootstrap(dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(),
-                                       self.trunc_buf.data_ptr(), lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), fv.data_ptr(), fv.shape[0],
-                                       float(self.gamma), float(self.gae_lambda), T, N, adv.data_ptr(), ret.data_ptr(),
-                                       episodes.reward_scaling if episodes is not None else 1.0, carry, out, stream), "pc_gae_bootstrap")
-            return adv, ret
+        rows = (dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(), self.trunc_buf.data_ptr(),
+                lv.data_ptr(), lt.data_ptr(), ltr.data_ptr())
+        scan = (float(self.gamma), float(self.gae_lambda), T, N, adv.data_ptr(), ret.data_ptr())
+        fv = None if final_values is None else final_values.detach()
+        assert fv is None or (fv.dtype == torch.float32 and fv.is_contiguous() and fv.device == self.device and fv.dim() == 2
+                              and fv.shape[1] == N)
+        scale, carry, out = 1.0, None, None
         if episodes is not None:
             assert episodes.num_envs == N and episodes.device == torch.device("cuda", dev)
-            check(lib.pc_gae_episodes(dev, self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(),
-                                      self.trunc_buf.data_ptr(), lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), float(self.gamma),
-                                      float(self.gae_lambda), T, N, adv.data_ptr(), ret.data_ptr(), episodes.reward_scaling,
-                                      episodes.carry.data_ptr(), episodes.out.data_ptr(), stream), "pc_gae_episodes")
-            return adv, ret
-        check(lib.pc_gae(self.device.index if self.device.index is not None else torch.cuda.current_device(),
-                         self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.term_buf.data_ptr(), self.trunc_buf.data_ptr(),
-                         lv.data_ptr(), lt.data_ptr(), ltr.data_ptr(), float(self.gamma), float(self.gae_lambda), T, N,
-                         adv.data_ptr(), ret.data_ptr(), stream), "pc_gae")
+            scale, carry, out = episodes.reward_scaling, episodes.carry.data_ptr(), episodes.out.data_ptr()
+        if fv is not None:
+            check(lib.pc_gae_bootstrap(*rows, fv.data_ptr(), fv.shape[0], *scan, scale, carry, out, stream), "pc_gae_bootstrap")
+        elif episodes is not None:
+            check(lib.pc_gae_episodes(*rows, *scan, scale, carry, out, stream), "pc_gae_episodes")
+        else:
+            check(lib.pc_gae(*rows, *scan, stream), "pc_gae")
         return adv, ret
 
     def get(self):

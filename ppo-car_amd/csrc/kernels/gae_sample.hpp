@@ -1,91 +1,48 @@
 // gae_sample.hpp -- part of the single translation unit ppocar.hip (included there, in order; not a stand-alone header).
-// K3 gae_kernel (Buffer.calculate_advantages) and K4 sample_kernel (Categorical sample / log_prob / entropy, Philox).
+// K3 gae_kernel<ADV, BOOT, EPI, STEPS> (the reverse scan: GAE and episode statistics) and K4 sample_kernel (Categorical
+// sample / log_prob / entropy, Philox).
 #pragma once
 
 // ------------------------------------------------------------------------------------------
-// K3: GAE(lambda), buffer.py:36-64.  One lane per env, serial in t (the recurrence), rows
-// coalesced across envs.  Operation order = torch's, one float32 rounding per op (no FMA):
+// K3: the reverse scan over the rollout buffer, gae_kernel<ADV, BOOT, EPI, STEPS>.  One lane per env, serial in t (the
+// recurrence), rows coalesced across envs.  Instances (the rest are rejected by the static_asserts):
+//   K3   <1,0,0,0>  GAE(lambda), buffer.py:36-64 (pc_gae)
+//   K3e  <1,0,1,0>  K3 plus the episode statistics (pc_gae_episodes)
+//   K3b  <1,1,0,0>  K3 with the truncation bootstrap (pc_gae_bootstrap)
+//        <1,1,1,0>  K3b plus the episode statistics (pc_gae_bootstrap with carry / out)
+//   K3e  <0,0,1,0>  the episode statistics alone, Buffer layout (pc_episode_stats, PC_EPISODE_BUFFER)
+//        <0,0,1,1>  the same, step layout (pc_episode_stats, PC_EPISODE_STEPS)
+// ADV: GAE.  Operation order = torch's, one float32 rounding per op (no FMA):
 //   delta    = (rew[t] + (gamma * next_val) * term_mask) - val[t]                       :60
 //   last_gae = delta + (((gamma*lambda) * term_mask) * trunc_mask) * last_gae           :61
+// Every ADV instance runs these float32 operations in this order, so adv / ret are K3's bits whatever else the launch does.
+// EPI: EpisodeAcc (below) on the rows already in registers -- no added HBM traffic per transition.
+// BOOT: at a truncated step t -- the trunc flag in row t + 1, or last_trunc for t = T - 1 -- next_val is V(final observation) from
+// final_val[t / PC_TIME_LIMIT] instead of val[t + 1] / last_val (which gymnasium's same-step auto-reset made V(reset observation));
+// every float32 operation and its order stay K3's, and so does the trace cut (trunc_mask).  final_val's values are used only at
+// truncated steps.  Each block of U rows loads the (at most two) slots its steps lie in together with its rows: a load per
+// truncation inside the recurrence made every wave wait for its outstanding stores (1.31 x K3); these are two coalesced
+// L2-resident words per env and block, issued with the rows.
+// STEPS (EPI alone): false, the Buffer layout: step t's flags in row t + 1, step T - 1's in last_* (row 0's are never used);
+// true: flags[t] belong to rew[t] (pc_env_step / pc_env_step_many rows), last_* are not read.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ rew, const float* __restrict__ val,
-                                                  const float* __restrict__ term, const float* __restrict__ trunc,
-                                                  const float* __restrict__ last_val, const float* __restrict__ last_term,
-                                                  const float* __restrict__ last_trunc, const float g, const float gl,
-                                                  const int64_t T, const int64_t N, float* __restrict__ adv,
-                                                  float* __restrict__ ret) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    float next_val = last_val[e];             // :53
-    float tmask = 1.0f - last_term[e];        // :54
-    float trmask = 1.0f - last_trunc[e];      // :55
-    float last_gae = 0.0f;
-    constexpr int U = 8;  // rows in flight per lane: the loads do not depend on the recurrence
-    int64_t t = T - 1;
-    for (; t >= U - 1; t -= U) {
-        float r[U], v[U], tm[U], tr[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            r[j] = rew[off];
-            v[j] = val[off];
-            tm[j] = term[off];
-            tr[j] = trunc[off];
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            float tmp = g * next_val;
-            tmp = tmp * tmask;
-            float delta = r[j] + tmp;
-            delta = delta - v[j];
-            float c = gl * tmask;
-            c = c * trmask;
-            c = c * last_gae;
-            last_gae = delta + c;
-            adv[off] = last_gae;           // :62
-            ret[off] = last_gae + v[j];    // :63
-            next_val = v[j];
-            tmask = 1.0f - tm[j];
-            trmask = 1.0f - tr[j];
-        }
-    }
-    for (; t >= 0; --t) {
-        const int64_t off = t * N + e;
-        const float r = rew[off], v = val[off];
-        float tmp = g * next_val;
-        tmp = tmp * tmask;
-        float delta = r + tmp;
-        delta = delta - v;
-        float c = gl * tmask;
-        c = c * trmask;
-        c = c * last_gae;
-        last_gae = delta + c;
-        adv[off] = last_gae;
-        ret[off] = last_gae + v;
-        next_val = v;
-        tmask = 1.0f - term[off];
-        trmask = 1.0f - trunc[off];
-    }
-}
 
-// ------------------------------------------------------------------------------------------
-// K3e: episode statistics (gymnasium's RecordEpisodeStatistics, plus gates and laps) from the rows K3 streams.
-// One lane per env, serial in t, REVERSE like K3: a boundary after step t (its terminated or truncated flag) closes the
-// segment to its right; the right-most closed segment is the new carry, every other one a finished episode; the left-most
-// segment adds the carry-in (the episode in progress when the window began) and finishes at the first boundary.
+// Episode statistics (gymnasium's RecordEpisodeStatistics, plus gates and laps) from the rows the scan streams.
+// REVERSE like K3: a boundary after step t (its terminated or truncated flag) closes the segment to its right; the right-most
+// closed segment is the new carry, every other one a finished episode; the left-most segment adds the carry-in (the episode in
+// progress when the window began) and finishes at the first boundary.
 //   Decoding: the reward is (float)(rw * s) with rw a sum of the reference's constants (car_env.py:700-748: 0.01 forward,
 //   +1 gate, +10 lap, -3 crash), so k = rint(r / s) is one of {0, 1, 11, -3, -2, 8} with a margin >= 0.49:
 //   a gate iff k in {1, 11, -2, 8}, a lap iff k in {11, 8}.
 //   Exactness: every float32 reward is an integer multiple of u = ulp(f32(0.01 s)) (no reward is smaller in magnitude
 //   and not zero).  An episode is at most 1000 steps (car_env.py:749), so every partial sum of one episode -- and of a
 //   window of T <= 1024 steps plus its carry -- stays below ~2000 * 11.01 / 0.01 * 2^24 u < 2^45 u < 2^53 u: the float64
-//   sums are EXACT, in any order.  The reverse scan here and a forward numpy sum give the same bits.
+//   sums are EXACT, in any order.  The reverse scan here and a forward numpy sum give the same bits, and the fused instances
+//   (K3e, K3b with carry / out) give the standalone one's.
 // Outputs (float64, structure of arrays, ACCUMULATED into what the caller initialised):
 //   out[0..6][N]: finished episodes, sum of their scaled returns, of their lengths, gates, laps; min / max scaled return
 //   carry[0..3][N] (in / out): return, length, gates, laps of the episode in progress; length -1 = start not observed
 //   (the episode that closes from there is dropped, and the carry restarts at 0).
-// ------------------------------------------------------------------------------------------
 struct EpisodeAcc {
     double seg_ret = 0.0;               // the open segment: from the scan position to the nearest boundary on its right
     int seg_len = 0, seg_g = 0, seg_l = 0;
@@ -157,25 +114,64 @@ struct EpisodeAcc {
     }
 };
 
-// K3e fused: K3's recurrence (the same float32 operations in the same order: adv / ret bit-identical to gae_kernel) plus
-// EpisodeAcc on the rows already in registers -- no added HBM traffic per transition.
-__global__ __launch_bounds__(256) void gae_episode_kernel(const float* __restrict__ rew, const float* __restrict__ val,
-                                                          const float* __restrict__ term, const float* __restrict__ trunc,
-                                                          const float* __restrict__ last_val, const float* __restrict__ last_term,
-                                                          const float* __restrict__ last_trunc, const float g, const float gl,
-                                                          const int64_t T, const int64_t N, float* __restrict__ adv,
-                                                          float* __restrict__ ret, const double inv_s, double* __restrict__ carry,
-                                                          double* __restrict__ out) {
+template <bool ADV, bool BOOT, bool EPI, bool STEPS>
+__global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ rew, const float* __restrict__ val,
+                                                  const float* __restrict__ term, const float* __restrict__ trunc,
+                                                  const float* __restrict__ last_val, const float* __restrict__ last_term,
+                                                  const float* __restrict__ last_trunc, const float g, const float gl,
+                                                  const int64_t T, const int64_t N, float* __restrict__ adv,
+                                                  float* __restrict__ ret, const float* __restrict__ final_val, const double inv_s,
+                                                  double* __restrict__ carry, double* __restrict__ out) {
+    static_assert(ADV || EPI, "the scan computes GAE, episode statistics or both");
+    static_assert(!BOOT || ADV, "the truncation bootstrap changes only GAE");
+    static_assert(!STEPS || !ADV, "GAE reads the Buffer layout");
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    float next_val = last_val[e];
-    const float lt = last_term[e], ltr = last_trunc[e];
-    float tmask = 1.0f - lt;
-    float trmask = 1.0f - ltr;
-    bool done = (lt != 0.0f) | (ltr != 0.0f);
-    float last_gae = 0.0f;
+    // What step t reads from the step after it: K3's next_val and masks, and `done` (step t ended an episode; EPI, Buffer
+    // layout).  The step takes and returns it by value, with done as a float 0 / 1, so the state stays out of memory until the
+    // step is inlined.  That keeps K3's instructions and every instance's registers within the hand-written kernels' counts; a
+    // bool member or the two flags carried as floats cost time (profiles/gae_template_refactor.txt has the counts and timings).
+    struct State {
+        float next_val, tmask, trmask, last_gae, done;
+    } st{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (!STEPS) {
+        const float lt = last_term[e], ltr = last_trunc[e];
+        if constexpr (BOOT) st.next_val = ltr != 0.0f ? final_val[(T - 1) / PC_TIME_LIMIT * N + e] : last_val[e];
+        else if constexpr (ADV) st.next_val = last_val[e];     // :53
+        st.tmask = 1.0f - lt;                                   // :54
+        st.trmask = 1.0f - ltr;                                 // :55
+        st.done = ((lt != 0.0f) | (ltr != 0.0f)) ? 1.0f : 0.0f;
+    }
     EpisodeAcc acc;
-    constexpr int U = 8;
+    // step t: its row's rew, val, term, trunc; boot() is final_val of step t - 1's slot, read only when step t - 1 truncated
+    const auto step = [=, &acc](State s, const int64_t t, const float r, const float v, const float tm, const float tr,
+                                const auto& boot) {
+        if constexpr (EPI)
+            acc.step(r, STEPS ? (tm != 0.0f) | (tr != 0.0f) : s.done != 0.0f, inv_s);
+        else
+            (void)acc;      // (captured for the EPI instances)
+        if constexpr (ADV) {
+            const int64_t off = t * N + e;
+            float tmp = g * s.next_val;
+            tmp = tmp * s.tmask;
+            float delta = r + tmp;
+            delta = delta - v;
+            float c = gl * s.tmask;
+            c = c * s.trmask;
+            c = c * s.last_gae;
+            s.last_gae = delta + c;
+            adv[off] = s.last_gae;          // :62
+            ret[off] = s.last_gae + v;      // :63
+        }
+        if constexpr (BOOT) s.next_val = (tr != 0.0f && t >= 1) ? boot() : v;
+        else s.next_val = v;
+        s.tmask = 1.0f - tm;
+        s.trmask = 1.0f - tr;
+        s.done = ((tm != 0.0f) | (tr != 0.0f)) ? 1.0f : 0.0f;
+        return s;
+    };
+    constexpr int U = 8;  // rows in flight per lane: the loads do not depend on the recurrence
+    static_assert(U - 1 <= PC_TIME_LIMIT, "the remainder rows' bootstrap reads slot 0");
     int64_t t = T - 1;
     for (; t >= U - 1; t -= U) {
         float r[U], v[U], tm[U], tr[U];
@@ -183,175 +179,27 @@ __global__ __launch_bounds__(256) void gae_episode_kernel(const float* __restric
         for (int j = 0; j < U; ++j) {
             const int64_t off = (t - j) * N + e;
             r[j] = rew[off];
-            v[j] = val[off];
+            v[j] = ADV ? val[off] : 0.0f;
             tm[j] = term[off];
             tr[j] = trunc[off];
         }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            float tmp = g * next_val;
-            tmp = tmp * tmask;
-            float delta = r[j] + tmp;
-            delta = delta - v[j];
-            float c = gl * tmask;
-            c = c * trmask;
-            c = c * last_gae;
-            last_gae = delta + c;
-            adv[off] = last_gae;
-            ret[off] = last_gae + v[j];
-            acc.step(r[j], done, inv_s);
-            next_val = v[j];
-            tmask = 1.0f - tm[j];
-            trmask = 1.0f - tr[j];
-            done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
+        // BOOT: steps t - 1 .. t - U lie in slot sa from step sb on, in slot sa - 1 (or sa) below it
+        float fa = 0.0f, fb = 0.0f;
+        int64_t sb = 0;
+        if constexpr (BOOT) {
+            const int64_t sa = (t - 1) / PC_TIME_LIMIT;
+            sb = sa * PC_TIME_LIMIT;
+            fa = final_val[sa * N + e];
+            fb = final_val[(t - U > 0 ? t - U : 0) / PC_TIME_LIMIT * N + e];
         }
+#pragma unroll
+        for (int j = 0; j < U; ++j) st = step(st, t - j, r[j], v[j], tm[j], tr[j], [&] { return t - j - 1 >= sb ? fa : fb; });
     }
-    for (; t >= 0; --t) {
+    for (; t >= 0; --t) {   // t < U - 1 <= PC_TIME_LIMIT: step t - 1 lies in slot 0 (static_assert above)
         const int64_t off = t * N + e;
-        const float r = rew[off], v = val[off];
-        float tmp = g * next_val;
-        tmp = tmp * tmask;
-        float delta = r + tmp;
-        delta = delta - v;
-        float c = gl * tmask;
-        c = c * trmask;
-        c = c * last_gae;
-        last_gae = delta + c;
-        adv[off] = last_gae;
-        ret[off] = last_gae + v;
-        acc.step(r, done, inv_s);
-        next_val = v;
-        const float tmf = term[off], trf = trunc[off];
-        tmask = 1.0f - tmf;
-        trmask = 1.0f - trf;
-        done = (tmf != 0.0f) | (trf != 0.0f);
-    }
-    acc.finish(carry, out, e, N);
-}
-
-// K3b: K3 with the truncation bootstrap (pc_gae_bootstrap).  At a truncated step t -- the trunc flag in row t + 1, or last_trunc for
-// t = T - 1 -- next_val is V(final observation) from final_val[t / PC_TIME_LIMIT] instead of val[t + 1] / last_val (which gymnasium's
-// same-step auto-reset made V(reset observation)); every float32 operation and its order stay K3's, and so does the trace cut
-// (trunc_mask).  final_val's values are used only at truncated steps.  Each block of U rows loads the (at most two) slots its steps
-// lie in together with its rows: a load per truncation inside the recurrence made every wave wait for its outstanding stores
-// (1.31 x K3); these are two coalesced L2-resident words per env and block, issued with the rows.  EPI: K3e's episode statistics
-// on the same rows (EpisodeAcc, the same steps in the same order: pc_gae_episodes' bits).
-template <bool EPI>
-__global__ __launch_bounds__(256) void gae_bootstrap_kernel(const float* __restrict__ rew, const float* __restrict__ val,
-                                                            const float* __restrict__ term, const float* __restrict__ trunc,
-                                                            const float* __restrict__ last_val, const float* __restrict__ last_term,
-                                                            const float* __restrict__ last_trunc, const float* __restrict__ final_val,
-                                                            const float g, const float gl, const int64_t T, const int64_t N,
-                                                            float* __restrict__ adv, float* __restrict__ ret, const double inv_s,
-                                                            double* __restrict__ carry, double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    const float lt = last_term[e], ltr = last_trunc[e];
-    float next_val = ltr != 0.0f ? final_val[(T - 1) / PC_TIME_LIMIT * N + e] : last_val[e];
-    float tmask = 1.0f - lt;
-    float trmask = 1.0f - ltr;
-    bool done = (lt != 0.0f) | (ltr != 0.0f);
-    float last_gae = 0.0f;
-    EpisodeAcc acc;
-    constexpr int U = 8;
-    int64_t t = T - 1;
-    for (; t >= U - 1; t -= U) {
-        float r[U], v[U], tm[U], tr[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            r[j] = rew[off];
-            v[j] = val[off];
-            tm[j] = term[off];
-            tr[j] = trunc[off];
-        }
-        // steps t - 1 .. t - U: slot sa from step sb on, slot sa - 1 (or sa) below it
-        const int64_t sa = (t - 1) / PC_TIME_LIMIT, sb = sa * PC_TIME_LIMIT;
-        const float fa = final_val[sa * N + e];
-        const float fb = final_val[(t - U > 0 ? t - U : 0) / PC_TIME_LIMIT * N + e];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            float tmp = g * next_val;
-            tmp = tmp * tmask;
-            float delta = r[j] + tmp;
-            delta = delta - v[j];
-            float c = gl * tmask;
-            c = c * trmask;
-            c = c * last_gae;
-            last_gae = delta + c;
-            adv[off] = last_gae;
-            ret[off] = last_gae + v[j];
-            if constexpr (EPI) acc.step(r[j], done, inv_s);
-            // row t - j holds the flags of step t - j - 1: a truncation there bootstraps from its final observation
-            const int64_t s = t - j - 1;
-            next_val = (tr[j] != 0.0f && s >= 0) ? (s >= sb ? fa : fb) : v[j];
-            tmask = 1.0f - tm[j];
-            trmask = 1.0f - tr[j];
-            if constexpr (EPI) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
-        }
-    }
-    for (; t >= 0; --t) {
-        const int64_t off = t * N + e;
-        const float r = rew[off], v = val[off];
-        float tmp = g * next_val;
-        tmp = tmp * tmask;
-        float delta = r + tmp;
-        delta = delta - v;
-        float c = gl * tmask;
-        c = c * trmask;
-        c = c * last_gae;
-        last_gae = delta + c;
-        adv[off] = last_gae;
-        ret[off] = last_gae + v;
-        if constexpr (EPI) acc.step(r, done, inv_s);
-        const float tmf = term[off], trf = trunc[off];
-        next_val = (trf != 0.0f && t >= 1) ? final_val[(t - 1) / PC_TIME_LIMIT * N + e] : v;
-        tmask = 1.0f - tmf;
-        trmask = 1.0f - trf;
-        if constexpr (EPI) done = (tmf != 0.0f) | (trf != 0.0f);
+        st = step(st, t, rew[off], ADV ? val[off] : 0.0f, term[off], trunc[off], [&] { return final_val[e]; });
     }
     if constexpr (EPI) acc.finish(carry, out, e, N);
-}
-
-// K3e standalone: the same accounting without GAE.  STEPS = false: the Buffer layout (step t's flags in row t + 1, step
-// T - 1's in last_*; row 0 is never read); STEPS = true: flags[t] belong to rew[t] (pc_env_step / pc_env_step_many rows).
-template <bool STEPS>
-__global__ __launch_bounds__(256) void episode_kernel(const float* __restrict__ rew, const float* __restrict__ term,
-                                                      const float* __restrict__ trunc, const float* __restrict__ last_term,
-                                                      const float* __restrict__ last_trunc, const int64_t T, const int64_t N,
-                                                      const double inv_s, double* __restrict__ carry, double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    bool done = STEPS ? false : (last_term[e] != 0.0f) | (last_trunc[e] != 0.0f);
-    EpisodeAcc acc;
-    constexpr int U = 8;
-    int64_t t = T - 1;
-    for (; t >= U - 1; t -= U) {
-        float r[U], tm[U], tr[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int64_t off = (t - j) * N + e;
-            r[j] = rew[off];
-            tm[j] = term[off];
-            tr[j] = trunc[off];
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            if (STEPS) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
-            acc.step(r[j], done, inv_s);
-            if (!STEPS) done = (tm[j] != 0.0f) | (tr[j] != 0.0f);
-        }
-    }
-    for (; t >= 0; --t) {
-        const int64_t off = t * N + e;
-        const float r = rew[off];
-        if (STEPS) done = (term[off] != 0.0f) | (trunc[off] != 0.0f);
-        acc.step(r, done, inv_s);
-        if (!STEPS && t > 0) done = (term[off] != 0.0f) | (trunc[off] != 0.0f);
-    }
-    acc.finish(carry, out, e, N);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -8,10 +8,11 @@
 //                                       (train.py:65,68,185)
 //   K2  env_reset_kernel<T>             CarEnv.reset for every env (car_env.py:605-691); reset_obs_kernel<T> computes
 //                                       each track's constant reset observation once at create
-//   K3  gae_kernel                      Buffer.calculate_advantages (buffer.py:36-64)
-//   K3e gae_episode_kernel / episode_kernel<STEPS>   episode return, length, gates and laps on K3's rows (pc_gae_episodes) or alone
-//                                       (pc_episode_stats)
-//   K3b gae_bootstrap_kernel<EPI>       K3 with V(final observation) at time-limit truncations (pc_gae_bootstrap; EPI: K3e's statistics too)
+//   K3  gae_kernel<ADV, BOOT, EPI, STEPS>   the reverse scan over the rollout buffer, one template for:
+//       K3  <1,0,0,0>                   Buffer.calculate_advantages (buffer.py:36-64, pc_gae)
+//       K3e <1,0,1,0> / <0,0,1,STEPS>   episode return, length, gates and laps on K3's rows (pc_gae_episodes) or alone
+//                                       (pc_episode_stats, Buffer or step layout)
+//       K3b <1,1,EPI,0>                 K3 with V(final observation) at time-limit truncations (pc_gae_bootstrap; EPI: K3e's statistics too)
 //   K4  sample_kernel                   Categorical(logits).sample / log_prob / entropy (model.py:35-40)
 //   K5  policy_kernel<KS, SPLIT, PREC>  Agent.get_action_and_value(x) of the rollout (model.py:34-41): both MLPs on the
 //                                       matrix cores + the draw; policy_pack*_kernel build its LDS weight image
@@ -122,6 +123,16 @@ struct DeviceGuard {  // set the handle's device for the call, restore the calle
     }
     int dev_;
 };
+
+// device is an id the runtime knows.  Not part of DeviceGuard: the per-step entries construct a guard on every call and must not
+// pay for hipGetDeviceCount there.
+bool valid_device(int device) {
+    int count = 0;
+    return hipGetDeviceCount(&count) == hipSuccess && count >= 1 && device >= 0 && device < count;
+}
+
+// a reward scale whose inverse decodes the episode statistics' rewards: finite, positive, with a finite inverse
+bool valid_reward_scale(double s) { return std::isfinite(s) && s > 0.0 && std::isfinite(1.0 / s); }
 
 // Launch a 512-thread kernel with `lds` bytes of dynamic LDS.  Its limit is raised to 160 KB once per (kernel, device), not on every
 // call (pc_env_step is on the per-step path); device ids from 64 on have no bit in the set and raise it on every call.
@@ -941,8 +952,7 @@ int pc_env_create(int device, int64_t n_envs, int num_rays_nominal, const pc_tra
     if (track_id)
         for (int64_t i = 0; i < n_envs; ++i)
             if (track_id[i] >= n_tracks) return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     g_hip_err.clear();
@@ -1172,22 +1182,35 @@ int pc_env_set_state(pc_env* e, const double* px, const double* py, const double
     return PC_OK;
 }
 
+// The reverse scan (K3, K3e, K3b, gae_kernel in kernels/gae_sample.hpp) for the four entries below, whose arguments are already
+// checked.  The instance follows from the inputs: val (GAE), final_val (the truncation bootstrap), carry (episode statistics) and,
+// without val, the layout.
+static int gae_scan(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
+                    const float* last_term, const float* last_trunc, const float* final_val, double gamma, double lam, int64_t T,
+                    int64_t N, float* adv, float* ret, double reward_scale, double* carry, double* out, bool steps, void* stream) {
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    decltype(&gae_kernel<true, false, false, false>) k;
+    if (!val) k = steps ? gae_kernel<false, false, true, true> : gae_kernel<false, false, true, false>;
+    else if (final_val) k = carry ? gae_kernel<true, true, true, false> : gae_kernel<true, true, false, false>;
+    else k = carry ? gae_kernel<true, false, true, false> : gae_kernel<true, false, false, false>;
+    // gamma and gamma*lambda are Python floats that torch casts to float32 at the multiply
+    hipLaunchKernelGGL(k, dim3((int)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val, last_term,
+                       last_trunc, (float)gamma, (float)(gamma * lam), T, N, adv, ret, final_val, carry ? 1.0 / reward_scale : 1.0,
+                       carry, out);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
 int pc_gae(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
            const float* last_term, const float* last_trunc, double gamma, double lam, int64_t T, int64_t N, float* adv,
            float* ret, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!rew || !val || !term || !trunc || !last_val || !last_term || !last_trunc || !adv || !ret || T < 1 || N < 1)
         return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
-    DeviceGuard guard(device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int blocks = (int)((N + 255) / 256);
-    // gamma and gamma*lambda are Python floats that torch casts to float32 at the multiply
-    hipLaunchKernelGGL(gae_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val, last_term,
-                       last_trunc, (float)gamma, (float)(gamma * lam), T, N, adv, ret);
-    HIPCHK(hipGetLastError());
-    return PC_OK;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    return gae_scan(device, rew, val, term, trunc, last_val, last_term, last_trunc, nullptr, gamma, lam, T, N, adv, ret, 1.0, nullptr,
+                    nullptr, false, stream);
 }
 
 int pc_episode_stats(int device, const float* rew, const float* term, const float* trunc, const float* last_term,
@@ -1197,20 +1220,10 @@ int pc_episode_stats(int device, const float* rew, const float* term, const floa
     if (!rew || !term || !trunc || !carry || !out || T < 1 || N < 1) return PC_ERR_INVALID_ARG;
     if (layout != PC_EPISODE_BUFFER && layout != PC_EPISODE_STEPS) return PC_ERR_INVALID_ARG;
     if (layout == PC_EPISODE_BUFFER && (!last_term || !last_trunc)) return PC_ERR_INVALID_ARG;
-    if (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale)) return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
-    DeviceGuard guard(device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int blocks = (int)((N + 255) / 256);
-    if (layout == PC_EPISODE_STEPS)
-        hipLaunchKernelGGL(episode_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, term, trunc, last_term,
-                           last_trunc, T, N, 1.0 / reward_scale, carry, out);
-    else
-        hipLaunchKernelGGL(episode_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, term, trunc, last_term,
-                           last_trunc, T, N, 1.0 / reward_scale, carry, out);
-    HIPCHK(hipGetLastError());
-    return PC_OK;
+    if (!valid_reward_scale(reward_scale)) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    return gae_scan(device, rew, nullptr, term, trunc, nullptr, last_term, last_trunc, nullptr, 0.0, 0.0, T, N, nullptr, nullptr,
+                    reward_scale, carry, out, layout == PC_EPISODE_STEPS, stream);
 }
 
 int pc_gae_episodes(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
@@ -1219,16 +1232,10 @@ int pc_gae_episodes(int device, const float* rew, const float* val, const float*
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!rew || !val || !term || !trunc || !last_val || !last_term || !last_trunc || !adv || !ret || !carry || !out || T < 1 || N < 1)
         return PC_ERR_INVALID_ARG;
-    if (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale)) return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
-    DeviceGuard guard(device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int blocks = (int)((N + 255) / 256);
-    hipLaunchKernelGGL(gae_episode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
-                       last_term, last_trunc, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0 / reward_scale, carry, out);
-    HIPCHK(hipGetLastError());
-    return PC_OK;
+    if (!valid_reward_scale(reward_scale)) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    return gae_scan(device, rew, val, term, trunc, last_val, last_term, last_trunc, nullptr, gamma, lam, T, N, adv, ret, reward_scale,
+                    carry, out, false, stream);
 }
 
 int pc_gae_bootstrap(int device, const float* rew, const float* val, const float* term, const float* trunc, const float* last_val,
@@ -1240,20 +1247,10 @@ int pc_gae_bootstrap(int device, const float* rew, const float* val, const float
     if (slots < (T + PC_TIME_LIMIT - 1) / PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
     const bool epi = carry != nullptr || out != nullptr;
     if (epi && (!carry || !out)) return PC_ERR_INVALID_ARG;
-    if (epi && (!std::isfinite(reward_scale) || !(reward_scale > 0.0) || !std::isfinite(1.0 / reward_scale))) return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
-    DeviceGuard guard(device);
-    if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const int blocks = (int)((N + 255) / 256);
-    if (epi)
-        hipLaunchKernelGGL(gae_bootstrap_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
-                           last_term, last_trunc, final_val, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0 / reward_scale, carry, out);
-    else
-        hipLaunchKernelGGL(gae_bootstrap_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rew, val, term, trunc, last_val,
-                           last_term, last_trunc, final_val, (float)gamma, (float)(gamma * lam), T, N, adv, ret, 1.0, nullptr, nullptr);
-    HIPCHK(hipGetLastError());
-    return PC_OK;
+    if (epi && !valid_reward_scale(reward_scale)) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    return gae_scan(device, rew, val, term, trunc, last_val, last_term, last_trunc, final_val, gamma, lam, T, N, adv, ret, reward_scale,
+                    carry, out, false, stream);
 }
 
 int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, uint64_t offset, int64_t* actions,
@@ -1261,8 +1258,7 @@ int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, 
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!logits || !actions || !logprob || N < 1 || A < 1) return PC_ERR_INVALID_ARG;
     if (A > 16) return PC_ERR_UNSUPPORTED;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int blocks = (int)((N + 255) / 256);
@@ -1373,8 +1369,7 @@ static int policy_pack_impl(int device, int prec, int D, int H, int A, const flo
                             const float* cW1, const float* cb1, const float* cW2, const float* cb2, float* image, int* status, void* stream) {
     if (!aW1 || !ab1 || !aW2 || !ab2 || !cW1 || !cb1 || !cW2 || !cb2 || !image) return PC_ERR_INVALID_ARG;
     if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     if (status) HIPCHK(hipMemsetAsync(status, 0, sizeof(int), (hipStream_t)stream));     // (forms without scaled domains leave it 0: no operand of theirs saturates)
@@ -1397,8 +1392,7 @@ static int policy_act_impl(int device, int prec, int split_mode, const float* ob
                            float* logits_out, void* stream) {
     if (!obs || !image || !action || !logprob || !value || N < 1) return PC_ERR_INVALID_ARG;
     if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int KS = policy_ks(D);
@@ -1982,8 +1976,7 @@ extern "C" {
 int pc_xchg_create(int device, int rank, int world, int64_t n_floats, pc_xchg** out) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!out || world < 1 || world > XCHG_MAX_RANKS || rank < 0 || rank >= world || n_floats < 1 || n_floats > (1 << 24)) return PC_ERR_INVALID_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) return PC_ERR_NO_DEVICE;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     pc_xchg* x = new (std::nothrow) pc_xchg;

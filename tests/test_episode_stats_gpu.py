@@ -1,4 +1,4 @@
-"""Episode statistics on the GPU (K3e: gae_episode_kernel, episode_kernel): per env bit for bit against the forward numpy
+"""Episode statistics on the GPU (K3e: gae_kernel<1,0,1,0>, <0,0,1,STEPS>): per env bit for bit against the forward numpy
 reference of test_episode_stats_host.py on synthetic buffers, against the env's own gate count on real rollouts, through
 VecCarEnv(record_episode_statistics=True), and through the Trainer (PPOConfig.episode_stats) and train.py --episode-stats."""
 import io

@@ -1,4 +1,4 @@
-"""Truncation bootstrap on the GPU: gae_bootstrap_kernel (pc_gae_bootstrap) against a float32 torch restatement bit for bit, the
+"""Truncation bootstrap on the GPU: K3b gae_kernel<1,1,EPI,0> (pc_gae_bootstrap) against a float32 torch restatement bit for bit, the
 final-observation capture of every persistent rollout family (pc_rollout_final_obs) against the per-step kernel K1's final_obs, the
 value pass of both bootstrap_value arithmetics, the Trainer's three rollout paths, and train.py --truncation-bootstrap."""
 import json

@@ -1,13 +1,16 @@
 """Timing of the episode statistics (K3e) against the GAE scan it rides on, and of a whole epoch with and without them.
 
   python tools/episode_stats_timing.py kernels [T] [N] [reps]   pc_gae, pc_gae_episodes and pc_episode_stats (Buffer layout) launched in
-                                                               turn on the same rows, device-event times per launch (run it under
-                                                               `rocprofv3 --kernel-trace --stats` for the kernel times themselves)
+                                                               turn on the same rows (gae_kernel<1,0,0,0>, <1,0,1,0>, <0,0,1,0>),
+                                                               device-event times per launch (run it under `rocprofv3
+                                                               --kernel-trace --stats` for the kernel times themselves)
   python tools/episode_stats_timing.py epoch [N] [epochs]       Trainer epochs at the benchmark's shape with PPOConfig.episode_stats off
                                                                and on, alternating on one device
 
 One JSON line per mode on stdout.  HBM bytes are counted from the shapes: K3 reads rew, val, term, trunc and writes adv, ret (24 B per
-transition); K3e fused adds 88 B per env (carry in / out, out in / out); K3e alone reads 12 B per transition."""
+transition); K3e fused adds 88 B per env (carry in / out, out in / out); K3e alone reads 12 B per transition.  The JSON keys keep the
+names the kernels had when profiles/episode_stats_timing.json was recorded: gae_kernel = K3, gae_episode_kernel = K3e fused,
+episode_kernel = K3e alone."""
 import json
 import os
 import statistics

@@ -5,11 +5,13 @@ the two variants alternating.
                                                                      capture (pc_rollout_final_obs / pc_rollout), the trained policy
                                                                      (tests/golden/policy_trained.npz) from staggered time steps, so
                                                                      that every env that survives truncates once per 1000 steps
-  python tools/truncation_bootstrap_timing.py kernels [T] [N] [reps]   K3 gae_kernel against gae_bootstrap_kernel (plain and with the
-                                                                     episode statistics: against K3e) on the same rows
+  python tools/truncation_bootstrap_timing.py kernels [T] [N] [reps]   K3 gae_kernel<1,0,0,0> against K3b gae_kernel<1,1,0,0> (and
+                                                                     <1,1,1,0> against K3e <1,0,1,0>) on the same rows
   python tools/truncation_bootstrap_timing.py epoch [N] [epochs]       Trainer epochs at the benchmark's shape, off and on
 
-One JSON line per mode on stdout; times are medians of HIP-event intervals."""
+One JSON line per mode on stdout; times are medians of HIP-event intervals.  The JSON keys keep the names the kernels had when
+profiles/truncation_bootstrap_timing.json was recorded: gae_kernel = K3, gae_bootstrap_kernel = K3b, gae_episode_kernel = K3e,
+gae_bootstrap_episode_kernel = K3b with the episode statistics."""
 import json
 import os
 import statistics
