@@ -384,6 +384,48 @@ int pc_ppo_minibatch_prepared(int device, const float* prepared_mb, int B, int D
                               float* workspace, int apply, void* stream);
 
 
+/* ---- update diagnostics and the target-KL early stop (opt-in: the entry points above are untouched).  Per minibatch of B samples,
+ * from the very logratio_i = new_logprob_i - old_logprob_i and ratio_i = exp(logratio_i) the clipped loss is made of (CleanRL's
+ * ppo.py):
+ *   approx_kl = mean_i((ratio_i - 1) - logratio_i)          clipfrac = mean_i(|ratio_i - 1| > clip_ratio)
+ * and per epoch, over the whole rollout, explained_variance = 1 - Var(ret - val) / Var(ret) (population variances; NaN when
+ * Var(ret) == 0).  The *_diag forms of the minibatch step keep a device block diag[PC_DIAG_FLOATS]:
+ *   [0] sum of approx_kl over the steps evaluated   [1] sum of clipfrac over them   [2] steps evaluated   [3] steps applied
+ *   [4] stop flag (0 / 1)                           [5] approx_kl of the last step evaluated               [6..7] pad
+ * The stop (Stable-Baselines3's target_kl): a step whose approx_kl > 1.5 * target_kl is evaluated but NOT applied -- grad, param,
+ * the moments, the step counter and metrics stay as they are -- and raises the flag; every later *_diag launch sees the flag and
+ * writes nothing, until the caller zeroes the block (hipMemsetAsync on the same stream, at the head of every epoch).  The flag
+ * is device memory read and written by the launches of one stream: no host round trip, so a captured graph of a whole epoch is
+ * replayed unchanged.  target_kl <= 0 or NaN: never stop (diagnostics only).  Without a stop, param / grad / exp_avg / exp_avg_sq /
+ * step_count / metrics get the bits of the plain entry points.
+ * pc_ppo_minibatch_diag / _prepared_diag: workspace of pc_ppo_diag_workspace_floats(B, D, H, A) floats (the plain layout plus a
+ * second per-workgroup partial); apply == 2 (the multi-rank form: the ranks would have to agree on the stop) is
+ * PC_ERR_UNSUPPORTED.  pc_ppo_loss_diag books the step as above (a stopping step still writes dlogits / dvalues);
+ * pc_clip_adam_diag is pc_clip_adam that returns at once when diag[4] != 0.  diag == NULL: PC_ERR_INVALID_ARG.
+ * pc_explained_variance: val / ret [M] float32, float64 accumulation about a shift with pairwise (Chan) merges, not
+ * E[x^2] - E[x]^2; two launches in a fixed order (deterministic); workspace: pc_explained_variance_workspace_doubles(device)
+ * doubles; out[5] = (mean(ret), M2(ret), mean(ret - val), M2(ret - val), explained_variance), M2 = the sum of squared deviations
+ * = M * Var.  NULL arrays or M < 1: PC_ERR_INVALID_ARG, checked before any device call. */
+#define PC_DIAG_FLOATS 8
+int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A);
+int pc_ppo_minibatch_diag(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
+                          const float* old_logprob, const float* adv, const float* ret, float* param, float* grad, float* exp_avg,
+                          float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef, double ent_coef,
+                          double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
+                          float* diag, double target_kl, void* stream);
+int pc_ppo_minibatch_prepared_diag(int device, const float* prepared_mb, int B, int D, int H, int A, float* param, float* grad, float* exp_avg,
+                                   float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef,
+                                   double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics,
+                                   float* workspace, int apply, float* diag, double target_kl, void* stream);
+int pc_ppo_loss_diag(int device, const float* logits, const float* values, const float* act, const float* old_logprob,
+                     const float* adv, const float* ret, int B, int A, double clip_ratio, double vf_coef, double ent_coef,
+                     float* dlogits, float* dvalues, float* metrics, float* diag, double target_kl, void* stream);
+int pc_clip_adam_diag(int device, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev,
+                      int64_t n, double max_norm, double grad_scale, double beta1, double beta2, double eps, const float* diag,
+                      void* stream);
+int64_t pc_explained_variance_workspace_doubles(int device);
+int pc_explained_variance(int device, const float* val, const float* ret, int64_t M, double* workspace, double* out, void* stream);
+
 /* The whole minibatch loop of one epoch (train.py:223-261) over n_mb prepared minibatches (consecutive blocks of
  * pc_ppo_prepared_floats(B, D) floats at `prepared`), with the clip + Adam step of minibatch i taken by the forward / backward
  * launch of minibatch i + 1 as it loads the parameters (every workgroup needs all of them anyway; workgroup 0 writes the new

@@ -105,6 +105,94 @@ __global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict_
     }
 }
 
+
+// Update diagnostics (the *_diag entry points; the plain kernels are untouched).  Per minibatch, from the very logratio = new_lp - old_lp
+// and r = exp(logratio) the loss is made of (CleanRL's ppo.py):
+//   approx_kl = mean((r - 1) - logratio)          clipfrac = mean(|r - 1| > clip)
+// and the block diag[PC_DIAG_FLOATS]: [0] sum of approx_kl over the steps evaluated, [1] sum of clipfrac, [2] steps evaluated,
+// [3] steps applied, [4] stop flag, [5] approx_kl of the last step evaluated.  kl_stop > 0 (= 1.5 target_kl, SB3's rule): a step whose
+// approx_kl exceeds it raises the flag INSTEAD of being applied; every later launch of the epoch reads the flag first and returns.
+// The flag is plain device memory written by one lane with an ordinary store and read by later launches of the same stream.
+struct DiagSums { float kl, clipfrac; };
+// the owner of `diag` (one thread of one workgroup) books an evaluated step; true = the step is applied
+__device__ __forceinline__ bool diag_book(float* __restrict__ diag, const DiagSums d, const float kl_stop) {
+    const bool stop = kl_stop > 0.0f && d.kl > kl_stop;
+    diag[0] += d.kl;
+    diag[1] += d.clipfrac;
+    diag[2] += 1.0f;
+    diag[5] = d.kl;
+    if (stop) diag[4] = 1.0f;
+    else diag[3] += 1.0f;
+    return !stop;
+}
+
+// K7d: K7 with the diagnostics (its own kernel: K7 above stays as it is).  The same loss and gradient operations in the same order.
+template <int AMAX>
+__global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __restrict__ logits, const float* __restrict__ values,
+                                                             const float* __restrict__ act, const float* __restrict__ old_lp,
+                                                             const float* __restrict__ adv, const float* __restrict__ ret, const int B,
+                                                             const int A, const float clip, const float vf, const float ec,
+                                                             float* __restrict__ dlogits, float* __restrict__ dvalues,
+                                                             float* __restrict__ metrics, float* __restrict__ diag, const float kl_stop) {
+    __shared__ float sh[16];
+    if (diag[4] != 0.0f) return;   // (uniform) the epoch's update has stopped
+    const int i = threadIdx.x;
+    const bool on = i < B;
+    const float invB = 1.0f / (float)B;
+    const float a_raw = on ? adv[i] : 0.0f;
+    const float mean = block_sum(a_raw, sh) * invB;
+    const float dev = on ? a_raw - mean : 0.0f;
+    const float var = block_sum(dev * dev, sh) / (float)(B - 1);   // unbiased, as Tensor.std() (train.py:239)
+    const float sd = fmaxf(sqrtf(var), 1e-5f);                     // torch.max(std, 1e-5) (train.py:239-240)
+    float pl = 0.0f, vl = 0.0f, ent = 0.0f, kl = 0.0f, clipped = 0.0f;
+    if (on) {
+        float l[AMAX];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < AMAX; ++k) {
+            l[k] = k < A ? logits[i * A + k] : -INFINITY;
+            mx = fmaxf(mx, l[k]);
+        }
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < AMAX; ++k) sum += k < A ? expf(l[k] - mx) : 0.0f;
+        const float lse = mx + logf(sum);
+        const int a = (int)act[i];
+        float new_lp = 0.0f;
+        float pk[AMAX], lpk[AMAX];
+#pragma unroll
+        for (int k = 0; k < AMAX; ++k) {
+            lpk[k] = k < A ? l[k] - lse : 0.0f;
+            pk[k] = k < A ? expf(lpk[k]) : 0.0f;
+            ent -= pk[k] * lpk[k];
+            if (k == a) new_lp = lpk[k];
+        }
+        const float r = expf(new_lp - old_lp[i]);                                  // :235
+        kl = (r - 1.0f) - (new_lp - old_lp[i]);
+        clipped = fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+        const float An = dev / sd;                                                 // :238-240
+        const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
+        const float pl1 = -An * r, pl2 = -An * rc;                                 // :243-244
+        pl = fmaxf(pl1, pl2);                                                      // :245
+        const float dv = values[i] - ret[i];
+        vl = 0.5f * dv * dv;                                                       // :249
+        const float g_lp = (pl1 >= pl2 ? -An : 0.0f) * r * invB;
+        dvalues[i] = vf * dv * invB;
+#pragma unroll
+        for (int k = 0; k < AMAX; ++k)
+            if (k < A) dlogits[i * A + k] = g_lp * ((k == a ? 1.0f : 0.0f) - pk[k]) + ec * invB * pk[k] * (lpk[k] + ent);
+    }
+    const float s_pl = block_sum(pl, sh) * invB, s_vl = block_sum(vl, sh) * invB, s_en = block_sum(ent, sh) * invB;
+    const DiagSums d{block_sum(kl, sh) * invB, block_sum(clipped, sh) * invB};
+    if (i == 0 && !diag_book(diag, d, kl_stop)) return;   // a stopping step adds nothing to the metrics either
+    if (i == 0) {
+        metrics[0] += s_pl;
+        metrics[1] += s_vl;
+        metrics[2] += s_en;
+        metrics[3] += s_pl + vf * s_vl - ec * s_en;                                // :255
+    }
+}
+
 // K8: nn.utils.clip_grad_norm_(params, max_norm) (train.py:260) + Adam.step() (train.py:261, lr from the device,
 // eps 1e-5, betas (0.9, 0.999), no weight decay / amsgrad) over the flat parameter bucket, one workgroup.
 // grad_scale folds the 1/world_size of the gradient average in.  state[0] = step count (float), updated here.
@@ -114,6 +202,39 @@ __global__ __launch_bounds__(1024) void clip_adam_kernel(float* __restrict__ par
                                                          const int n, const float max_norm, const float grad_scale,
                                                          const float beta1, const float beta2, const float eps) {
     __shared__ float sh[16];
+    float ss = 0.0f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const float g = grad[i] * grad_scale;
+        ss += g * g;
+    }
+    const float total_norm = sqrtf(block_sum(ss, sh));
+    const float coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);   // clip_coef_clamped
+    const float step = step_count[0] + 1.0f;
+    const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
+    const float step_size = lr_dev[0] / bc1;
+    const float bc2_sqrt = sqrtf(bc2);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const float g = grad[i] * grad_scale * coef;
+        grad[i] = g;                                                   // clip_grad_norm_ scales the grads in place
+        const float m = exp_avg[i] + (1.0f - beta1) * (g - exp_avg[i]);            // exp_avg.lerp_(grad, 1 - beta1)
+        const float v = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;            // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+        exp_avg[i] = m;
+        exp_avg_sq[i] = v;
+        const float denom = sqrtf(v) / bc2_sqrt + eps;
+        param[i] -= step_size * (m / denom);                                        // param.addcdiv_(exp_avg, denom, -step_size)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) step_count[0] = step;
+}
+// K8d: K8 that returns at once when the update has stopped (its own kernel: K8 above stays as it is)
+__global__ __launch_bounds__(1024) void clip_adam_diag_kernel(float* __restrict__ param, float* __restrict__ grad,
+                                                              float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                              float* __restrict__ step_count, const float* __restrict__ lr_dev,
+                                                              const int n, const float max_norm, const float grad_scale,
+                                                              const float beta1, const float beta2, const float eps,
+                                                              const float* __restrict__ diag) {
+    __shared__ float sh[16];
+    if (diag[4] != 0.0f) return;   // (uniform) stopped: parameters, moments, gradient and step counter stay
     float ss = 0.0f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float g = grad[i] * grad_scale;
@@ -278,15 +399,20 @@ __global__ __launch_bounds__(256) void ppo_prepare_kernel(const int64_t* __restr
 // unrolled 16-slot loops is a v_cndmask per slot and sample and the FMAs of the unused slots are executed (backward: 219
 // selects + 112 FMAs per thread); the same operations in the same order either way.
 // DC > 0: likewise the observation width (6 + 12 / 17 / 33 rays).
-template <int DMAX, int AC = 0, int DC = 0, bool DEFER = false>
+// DIAG: the update-diagnostics form (ppo_loss_body's comment): the stop flag is read first, and each workgroup also leaves the sums of
+// its samples' KL terms and clipped-sample counts in diag_partial[wg][2] -- a second partial: (pl, vl, ent, -) keeps its layout.
+template <int DMAX, int AC = 0, int DC = 0, bool DEFER = false, bool DIAG = false>
 __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __restrict__ idx, const int B, const int D_rt, const int A_rt,
                                                 const float* __restrict__ obs, const float* __restrict__ act,
                                                 const float* __restrict__ old_lp, const float* __restrict__ adv,
                                                 const float* __restrict__ ret, const float* __restrict__ param,
                                                 const float clip, const float vf, const float ec,
                                                 float* __restrict__ partial, float* __restrict__ metric_partial,
-                                                const float* __restrict__ prep, const AdamDefer df) {
+                                                const float* __restrict__ prep, const AdamDefer df,
+                                                const float* __restrict__ diag = nullptr, float* __restrict__ diag_partial = nullptr) {
     constexpr int H = 256, S = FB_S, LDT = DMAX + 1, LDH = H + 1;
+    static_assert(!(DIAG && DEFER), "the deferred chain has no diagnostics form");
+    if constexpr (DIAG) if (diag[4] != 0.0f) return;   // (uniform) the epoch's update has stopped: this launch costs its latency only
     const int A = AC > 0 ? AC : A_rt, D = DC > 0 ? DC : D_rt;
     static_assert(DC <= DMAX, "observation width");
     // Everything in this kernel is latency: a minibatch is 44 MFLOP.  So: every global access coalesced (the [H][D]
@@ -296,7 +422,7 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
     __shared__ float sX[S][DMAX];
     __shared__ float sOut[S][16];
     __shared__ float sDout[S][16];
-    __shared__ float sMet[S][3];
+    __shared__ float sMet[S][DIAG ? 5 : 3];                               // pl, vl, ent (, KL term, clipped) of my samples
     __shared__ float sSmp[S][4];                                          // act, old_lp, adv, ret of my samples
     __shared__ __attribute__((aligned(16))) float sT[H * LDT > 2 * S * LDH + 16 * LDH + 4 * S * 16 ? H * LDT : 2 * S * LDH + 16 * LDH + 4 * S * 16];
     static_assert(H * LDT >= H * DMAX + 8, "the tile holds one [H][D] block in natural order plus an alignment shift");
@@ -609,6 +735,10 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
             sMet[sidx][0] = live ? pl : 0.0f;
             sMet[sidx][1] = live ? vl : 0.0f;
             sMet[sidx][2] = live ? ent : 0.0f;
+            if constexpr (DIAG) {
+                sMet[sidx][3] = live ? (r - 1.0f) - (new_lp - sSmp[sidx][1]) : 0.0f;
+                sMet[sidx][4] = live && fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+            }
         }
 #undef PC_ROW_ROR
     }
@@ -678,6 +808,12 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
         for (int sidx = 0; sidx < S; ++sidx) t += sMet[sidx][u];
         metric_partial[wg * 4 + u] = t;
     }
+    if constexpr (DIAG) if (u >= 3 && u < 5) {
+        float t = 0.0f;
+#pragma unroll
+        for (int sidx = 0; sidx < S; ++sidx) t += sMet[sidx][u];
+        diag_partial[wg * 2 + (u - 3)] = t;
+    }
     PC_STAMP_U(8)
 #pragma unroll
     for (int net = 0; net < 2; ++net) {
@@ -709,16 +845,43 @@ __global__ __launch_bounds__(256) void ppo_fwdbwd_kernel(const int64_t* __restri
                                                          const float* __restrict__ prep, const AdamDefer df) {
     ppo_fwdbwd_body<DMAX, AC, DC, DEFER>(blockIdx.x, idx, B, D, A, obs, act, old_lp, adv, ret, param, clip, vf, ec, partial, metric_partial, prep, df);
 }
+template <int DMAX, int AC = 0, int DC = 0>
+__global__ __launch_bounds__(256) void ppo_fwdbwd_diag_kernel(const int64_t* __restrict__ idx, const int B, const int D, const int A,
+                                                              const float* __restrict__ obs, const float* __restrict__ act,
+                                                              const float* __restrict__ old_lp, const float* __restrict__ adv,
+                                                              const float* __restrict__ ret, const float* __restrict__ param,
+                                                              const float clip, const float vf, const float ec,
+                                                              float* __restrict__ partial, float* __restrict__ metric_partial,
+                                                              const float* __restrict__ prep, const float* __restrict__ diag,
+                                                              float* __restrict__ diag_partial) {
+    ppo_fwdbwd_body<DMAX, AC, DC, false, true>(blockIdx.x, idx, B, D, A, obs, act, old_lp, adv, ret, param, clip, vf, ec, partial, metric_partial, prep,
+                                               AdamDefer{}, diag, diag_partial);
+}
 
 // K11: flat_grad[i] = sum_p partial[p][i] (fixed order: deterministic); block-wise squared-norm partials for the clip;
 // block 0 folds the metric partials into the running sums (train.py:263-266) and advances the Adam step counter.
+// DIAG: the flag and K10's diag_partial are REQUESTED with the gradient loads and used after them (only the writes wait for the
+// decision: a fold in front of the loads put three dependent round trips at the head of a latency-bound launch).  Every workgroup
+// folds the partial (n_part <= 128 pairs, index order: the same two floats everywhere) and returns without a write when the flag is up
+// or this step's approx_kl exceeds kl_stop -- grad, norm partials, metrics and the step counter stay as they are; workgroup 0 books the
+// step in `diag` and raises the flag.  Every wave has written its part of the LDS copy and passed the barrier BEFORE any wave looks at
+// the flag, so a wave of the stopping launch that already sees workgroup 0's flag leaves, and the others, which fold the same d, leave
+// on d: the same outcome whatever the timing.
+template <bool DIAG = false>
 __device__ __forceinline__ void grad_reduce_body(const int blk, const float* __restrict__ partial, const int n_part, const int n,
                                                           const int HD, const int mid_end, const int n_pad,
                                                           float* __restrict__ grad, float* __restrict__ norm_partial,
                                                           const float* __restrict__ metric_partial, const int B, const float vf,
-                                                          const float ec, float* __restrict__ metrics, float* __restrict__ step_count) {
+                                                          const float ec, float* __restrict__ metrics, float* __restrict__ step_count,
+                                                          float* __restrict__ diag = nullptr, const float* __restrict__ diag_partial = nullptr,
+                                                          const float kl_stop = 0.0f) {
     __shared__ float sh[16];
     __syncthreads();  // (shared scratch reuse when called in a loop)
+    float dg_val = 0.0f, flag_val = 0.0f;
+    if constexpr (DIAG) {
+        if ((int)threadIdx.x < 2 * n_part) dg_val = diag_partial[threadIdx.x];     // n_part <= 128 (B <= 1024, 8 samples per workgroup)
+        flag_val = diag[4];
+    }
     const int i = blk * blockDim.x + threadIdx.x;
     // workgroup 0 also folds the metric partials: their first 256 words are requested now, under the gradient loads
     const float mp_first = (blk == 0 && (int)threadIdx.x < n_part * 4) ? metric_partial[threadIdx.x] : 0.0f;
@@ -750,6 +913,22 @@ __device__ __forceinline__ void grad_reduce_body(const int blk, const float* __r
             for (int j = 0; j < 8; ++j) g += t[j];
         }
         for (; pidx < n_part; ++pidx) g += pp[(size_t)pidx * n_pad];
+    }
+    if constexpr (DIAG) {
+        __shared__ __attribute__((aligned(8))) float sDg[256];
+        sDg[threadIdx.x] = dg_val;                        // (every thread of every wave: slots past 2 n_part hold 0)
+        __syncthreads();
+        if (flag_val != 0.0f) return;                     // (per wave; see above)
+        float kl = 0.0f, nc = 0.0f;
+#pragma unroll 8
+        for (int p = 0; p < n_part; ++p) {
+            const float2 v = reinterpret_cast<const float2*>(sDg)[p];
+            kl += v.x;
+            nc += v.y;
+        }
+        const DiagSums d{kl / (float)B, nc / (float)B};
+        if (blk == 0 && threadIdx.x == 0) diag_book(diag, d, kl_stop);
+        if (kl_stop > 0.0f && d.kl > kl_stop) return;     // (uniform: every thread of every workgroup holds the same d)
     }
     if (i < n) grad[i] = g;
     const float ss = block_sum(g * g, sh);
@@ -790,14 +969,25 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
                                                           const float ec, float* __restrict__ metrics, float* __restrict__ step_count) {
     grad_reduce_body(blockIdx.x, partial, n_part, n, HD, mid_end, n_pad, grad, norm_partial, metric_partial, B, vf, ec, metrics, step_count);
 }
+__global__ __launch_bounds__(256) void grad_reduce_diag_kernel(const float* __restrict__ partial, const int n_part, const int n,
+                                                               const int HD, const int mid_end, const int n_pad,
+                                                               float* __restrict__ grad, float* __restrict__ norm_partial,
+                                                               const float* __restrict__ metric_partial, const int B, const float vf,
+                                                               const float ec, float* __restrict__ metrics, float* __restrict__ step_count,
+                                                               float* __restrict__ diag, const float* __restrict__ diag_partial,
+                                                               const float kl_stop) {
+    grad_reduce_body<true>(blockIdx.x, partial, n_part, n, HD, mid_end, n_pad, grad, norm_partial, metric_partial, B, vf, ec, metrics, step_count,
+                           diag, diag_partial, kl_stop);
+}
 
 // K12: clip_grad_norm_ + Adam, one element per thread; the squared norm arrives as per-block partials of K11 and
 // the step counter has already been advanced there.
+template <bool DIAG = false>
 __device__ __forceinline__ void adam_body(const int blk, const float* __restrict__ p_in, const float* __restrict__ m_in, const float* __restrict__ v_in,
                                           float* __restrict__ grad, float* __restrict__ p_out, float* __restrict__ m_out, float* __restrict__ v_out,
                                           const float* __restrict__ step_count, const float* __restrict__ lr_dev,
                                           const float* __restrict__ norm_partial, const int n_norm, const int n, const float max_norm,
-                                          const float beta1, const float beta2, const float eps) {
+                                          const float beta1, const float beta2, const float eps, const float* __restrict__ diag = nullptr) {
     // all loads first (cold misses: the operands were written by other workgroups), the norm partials once per
     // workgroup through LDS; every thread then sums them in index order
     __shared__ float sNorm[256];
@@ -806,6 +996,8 @@ __device__ __forceinline__ void adam_body(const int blk, const float* __restrict
     const float g_raw = live ? grad[i] : 0.0f;
     float m = live ? m_in[i] : 0.0f, v = live ? v_in[i] : 0.0f, p = live ? p_in[i] : 0.0f;
     const float step = step_count[0], lr = lr_dev[0];
+    float flag = 0.0f;
+    if constexpr (DIAG) flag = diag[4];        // requested with the other loads, used before the first write
     float ss = 0.0f;
     for (int j0 = 0; j0 < n_norm; j0 += 256) {
         __syncthreads();
@@ -816,6 +1008,7 @@ __device__ __forceinline__ void adam_body(const int blk, const float* __restrict
     }
     const AdamCoef ac = adam_coef(ss, step, lr, max_norm, beta1, beta2, eps);
     if (!live) return;
+    if constexpr (DIAG) if (flag != 0.0f) return;   // (uniform: K11 finished before this launch began) stopped or stopping: nothing is written
     grad[i] = g_raw * ac.coef;             // clip_grad_norm_ scales the grads in place
     adam_elem(ac, g_raw, p, m, v);
     m_out[i] = m;
@@ -832,6 +1025,14 @@ __global__ __launch_bounds__(256) void adam_kernel(const float* __restrict__ p_i
                                                    const int n_norm, const int n, const float max_norm, const float beta1,
                                                    const float beta2, const float eps) {
     adam_body(blockIdx.x, p_in, m_in, v_in, grad, p_out, m_out, v_out, step_count, lr_dev, norm_partial, n_norm, n, max_norm, beta1, beta2, eps);
+}
+__global__ __launch_bounds__(256) void adam_diag_kernel(const float* __restrict__ p_in, const float* __restrict__ m_in, const float* __restrict__ v_in,
+                                                        float* __restrict__ grad, float* __restrict__ p_out, float* __restrict__ m_out,
+                                                        float* __restrict__ v_out, const float* __restrict__ step_count,
+                                                        const float* __restrict__ lr_dev, const float* __restrict__ norm_partial,
+                                                        const int n_norm, const int n, const float max_norm, const float beta1,
+                                                        const float beta2, const float eps, const float* __restrict__ diag) {
+    adam_body<true>(blockIdx.x, p_in, m_in, v_in, grad, p_out, m_out, v_out, step_count, lr_dev, norm_partial, n_norm, n, max_norm, beta1, beta2, eps, diag);
 }
 
 

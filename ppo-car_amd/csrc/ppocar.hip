@@ -77,6 +77,7 @@
 #include "kernels/rollout.hpp"
 #include "kernels/env_steps.hpp"
 #include "kernels/update.hpp"
+#include "kernels/diagnostics.hpp"
 #include "kernels/exchange.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -1268,6 +1269,22 @@ int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, 
     return PC_OK;
 }
 
+// the compute-unit count of a device, asked once per device (ids from 64 on: 256).  The one cache of the library: two threads that
+// race on an entry store the same value.
+static int device_cus(int device, int* out) {
+    static std::atomic<int> n_cu[64];
+    if (device < 0 || device >= 64) { *out = 256; return PC_OK; }
+    int c = n_cu[device].load(std::memory_order_relaxed);
+    if (c == 0) {
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, device));
+        c = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        n_cu[device].store(c, std::memory_order_relaxed);
+    }
+    *out = c;
+    return PC_OK;
+}
+
 static int policy_ks(int D) { return D <= 20 ? 5 : (D <= 24 ? 6 : 10); }
 // Batches up to this size take the forms that cut the work of 32 envs over a whole workgroup (policy_kernel<SPLIT>,
 // rollout_small_kernel): n_envs / 32 workgroups, so 16384 envs are two rounds of 256 -- about what the 128-env big form
@@ -1397,13 +1414,9 @@ static int policy_act_impl(int device, int prec, int split_mode, const float* ob
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int KS = policy_ks(D);
     const size_t lds = (size_t)((prec ? polx_image_dwords(prec, pol_ng(KS)) : pol_image_padded(KS)) + 8 * 32 * 20) * sizeof(float);
-    static int n_cu[64] = {0};
-    if (device < 64 && n_cu[device] == 0) {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, device));
-        n_cu[device] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int cus = device < 64 ? n_cu[device] : 256;
+    int cus = 0;
+    const int cu_rc = device_cus(device, &cus);
+    if (cu_rc != PC_OK) return cu_rc;
     // too few 256-env workgroups to fill the chip: split the hidden tiles over the waves instead
     const bool split = split_mode < 0 ? N <= PC_SPLIT_MAX_ENVS : split_mode == 1;
     const int64_t chunks = split ? (N + 31) / 32 : (N + 255) / 256;
@@ -1476,6 +1489,64 @@ int pc_clip_adam(int device, float* param, float* grad, float* exp_avg, float* e
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     hipLaunchKernelGGL(clip_adam_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
                        lr_dev, (int)n, (float)max_norm, (float)grad_scale, (float)beta1, (float)beta2, (float)eps);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+// 1.5 x target_kl as the kernels' float threshold (SB3's rule); target_kl <= 0 or NaN: 0 = never stop
+static float kl_stop_of(double target_kl) { return target_kl > 0.0 ? (float)(1.5 * target_kl) : 0.0f; }
+
+int pc_ppo_loss_diag(int device, const float* logits, const float* values, const float* act, const float* old_logprob,
+                     const float* adv, const float* ret, int B, int A, double clip_ratio, double vf_coef, double ent_coef,
+                     float* dlogits, float* dvalues, float* metrics, float* diag, double target_kl, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!logits || !values || !act || !old_logprob || !adv || !ret || !dlogits || !dvalues || !metrics || !diag) return PC_ERR_INVALID_ARG;
+    if (B < 2 || B > 1024 || A < 1 || A > 16) return PC_ERR_UNSUPPORTED;
+    if (device < 0) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int threads = ((B + 63) / 64) * 64;
+    hipLaunchKernelGGL(ppo_loss_diag_kernel<16>, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, values, act, old_logprob, adv,
+                       ret, B, A, (float)clip_ratio, (float)vf_coef, (float)ent_coef, dlogits, dvalues, metrics, diag, kl_stop_of(target_kl));
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_clip_adam_diag(int device, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev,
+                      int64_t n, double max_norm, double grad_scale, double beta1, double beta2, double eps, const float* diag,
+                      void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr_dev || !diag || n < 1 || n > (1 << 26)) return PC_ERR_INVALID_ARG;
+    if (device < 0) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    hipLaunchKernelGGL(clip_adam_diag_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
+                       lr_dev, (int)n, (float)max_norm, (float)grad_scale, (float)beta1, (float)beta2, (float)eps, diag);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int64_t pc_explained_variance_workspace_doubles(int device) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    (void)device;        // (the same bound on every device: the grid is min(needed, 8 per compute unit, this))
+    return 5 * (int64_t)PC_EV_MAX_BLOCKS;
+}
+
+int pc_explained_variance(int device, const float* val, const float* ret, int64_t M, double* workspace, double* out, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!val || !ret || !workspace || !out || M < 1) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    int cus = 0;
+    const int cu_rc = device_cus(device, &cus);
+    if (cu_rc != PC_OK) return cu_rc;
+    const int64_t cap = std::min<int64_t>(8 * (int64_t)cus, PC_EV_MAX_BLOCKS);
+    const int64_t need = (M + 8 * 256 - 1) / (8 * 256);      // 8 samples per thread and pass
+    const int blocks = (int)std::max<int64_t>(1, std::min(need, cap));
+    const int vec = (((uintptr_t)val | (uintptr_t)ret) & 15) == 0;
+    hipLaunchKernelGGL(explained_variance_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, val, ret, M, vec, workspace);
+    hipLaunchKernelGGL(explained_variance_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, blocks, out);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
@@ -1770,10 +1841,16 @@ int64_t pc_ppo_workspace_floats(int B, int D, int H, int A) {
     return n_part * ((n_param + 3) & ~(int64_t)3) + n_part * 4 + (n_param + 255) / 256;
 }
 
+// the diagnostics forms append a second per-workgroup partial (sum of KL terms, clipped samples) to that layout
+int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
+    const int64_t base = pc_ppo_workspace_floats(B, D, H, A);
+    return base < 0 ? base : base + 2 * (int64_t)((B + FB_S - 1) / FB_S);
+}
+
 // the layout of pc_ppo_minibatch's workspace and the launches of one minibatch step
 struct MbPlan {
     int n_param, n_part, n_blk, n_pad, HD, mid_end;
-    float *partial, *metric_partial, *norm_partial;
+    float *partial, *metric_partial, *norm_partial, *diag_partial;
     MbPlan(int B, int D, int H, int A, float* workspace) {
         n_param = 2 * (H * D + H) + A * H + A + H + 1;
         n_part = (B + FB_S - 1) / FB_S;
@@ -1784,6 +1861,7 @@ struct MbPlan {
         partial = workspace;
         metric_partial = partial + (size_t)n_part * n_pad;
         norm_partial = metric_partial + n_part * 4;
+        diag_partial = norm_partial + n_blk;     // (pc_ppo_diag_workspace_floats: only the diagnostics forms touch it)
     }
 };
 
@@ -1800,6 +1878,19 @@ static void launch_fwdbwd(const MbPlan& pl, const int64_t* idx, const float* pre
     else if (A == 9 && D == 39) { if (df.grad) PC_FB(40, 9, 39, true); else PC_FB(40, 9, 39, false); }
     else if (D <= 24) PC_FB(24, 0, 0, false);
     else PC_FB(40, 0, 0, false);
+#undef PC_FB
+}
+static void launch_fwdbwd_diag(const MbPlan& pl, const int64_t* idx, const float* prep, int B, int D, int A, const float* obs, const float* act,
+                               const float* old_logprob, const float* adv, const float* ret, const float* param, double clip_ratio, double vf_coef,
+                               double ent_coef, const float* diag, hipStream_t st) {
+#define PC_FB(DM, ACV, DCV)                                                                                              \
+    hipLaunchKernelGGL((ppo_fwdbwd_diag_kernel<DM, ACV, DCV>), dim3(pl.n_part), dim3(256), 0, st, idx, B, D, A, obs, act, old_logprob, adv, ret, param, \
+                       (float)clip_ratio, (float)vf_coef, (float)ent_coef, pl.partial, pl.metric_partial, prep, diag, pl.diag_partial)
+    if (A == 9 && D == 23) PC_FB(24, 9, 23);       // (launch_fwdbwd's menu)
+    else if (A == 9 && D == 18) PC_FB(24, 9, 18);
+    else if (A == 9 && D == 39) PC_FB(40, 9, 39);
+    else if (D <= 24) PC_FB(24, 0, 0);
+    else PC_FB(40, 0, 0);
 #undef PC_FB
 }
 static bool mb_defer_shape(int D, int A) { return A == 9 && (D == 18 || D == 23 || D == 39); }
@@ -1820,17 +1911,30 @@ static int ppo_minibatch_impl(int device, const int64_t* idx, const float* prep,
                               const float* act, const float* old_logprob, const float* adv, const float* ret, float* param, float* grad,
                               float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio,
                               double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics,
-                              float* workspace, int apply, void* stream) {
+                              float* workspace, int apply, void* stream, float* diag = nullptr, double target_kl = 0.0) {
     if (!param || !grad || !metrics || !workspace) return PC_ERR_INVALID_ARG;
     if (!prep && (!idx || !obs || !act || !old_logprob || !adv || !ret)) return PC_ERR_INVALID_ARG;
     if (apply == 1 && (!exp_avg || !exp_avg_sq || !step_count || !lr_dev)) return PC_ERR_INVALID_ARG;
     if (apply == 2 && !step_count) return PC_ERR_INVALID_ARG;
     if (apply < 0 || apply > 2) return PC_ERR_INVALID_ARG;
     if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
+    if (diag && apply == 2) return PC_ERR_UNSUPPORTED;      // (the ranks of a multi-rank step would have to agree on the stop)
+    if (diag && device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const MbPlan pl(B, D, H, A, workspace);
     hipStream_t st = (hipStream_t)stream;
+    if (diag) {     // the diagnostics forms of the same three launches (update.hpp: DIAG)
+        launch_fwdbwd_diag(pl, idx, prep, B, D, A, obs, act, old_logprob, adv, ret, param, clip_ratio, vf_coef, ent_coef, diag, st);
+        hipLaunchKernelGGL(grad_reduce_diag_kernel, dim3(pl.n_blk), dim3(256), 0, st, pl.partial, pl.n_part, pl.n_param, pl.HD, pl.mid_end, pl.n_pad,
+                           grad, pl.norm_partial, pl.metric_partial, B, (float)vf_coef, (float)ent_coef, metrics, apply ? step_count : nullptr, diag,
+                           pl.diag_partial, kl_stop_of(target_kl));
+        if (apply == 1)
+            hipLaunchKernelGGL(adam_diag_kernel, dim3(pl.n_blk), dim3(256), 0, st, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count,
+                               lr_dev, pl.norm_partial, pl.n_blk, pl.n_param, (float)max_norm, (float)beta1, (float)beta2, (float)eps, diag);
+        HIPCHK(hipGetLastError());
+        return PC_OK;
+    }
     launch_fwdbwd(pl, idx, prep, B, D, A, obs, act, old_logprob, adv, ret, param, clip_ratio, vf_coef, ent_coef, AdamDefer{}, st);
     launch_reduce(pl, B, vf_coef, ent_coef, grad, metrics, apply ? step_count : nullptr, st);
     if (apply == 1) launch_adam(pl, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
@@ -1847,6 +1951,18 @@ int pc_ppo_minibatch(int device, const int64_t* idx, int B, int D, int H, int A,
     return ppo_minibatch_impl(device, idx, nullptr, B, D, H, A, obs, act, old_logprob, adv, ret, param, grad, exp_avg, exp_avg_sq,
                               step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics, workspace, apply,
                               stream);
+}
+
+int pc_ppo_minibatch_diag(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
+                          const float* old_logprob, const float* adv, const float* ret, float* param, float* grad, float* exp_avg,
+                          float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef, double ent_coef,
+                          double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
+                          float* diag, double target_kl, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!diag) return PC_ERR_INVALID_ARG;
+    return ppo_minibatch_impl(device, idx, nullptr, B, D, H, A, obs, act, old_logprob, adv, ret, param, grad, exp_avg, exp_avg_sq,
+                              step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics, workspace, apply,
+                              stream, diag, target_kl);
 }
 
 int64_t pc_ppo_prepared_floats(int B, int D) {
@@ -1879,6 +1995,16 @@ int pc_ppo_minibatch_prepared(int device, const float* prepared_mb, int B, int D
                               workspace, apply, stream);
 }
 
+int pc_ppo_minibatch_prepared_diag(int device, const float* prepared_mb, int B, int D, int H, int A, float* param, float* grad, float* exp_avg,
+                                   float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef,
+                                   double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics,
+                                   float* workspace, int apply, float* diag, double target_kl, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!prepared_mb || !diag) return PC_ERR_INVALID_ARG;
+    return ppo_minibatch_impl(device, nullptr, prepared_mb, B, D, H, A, nullptr, nullptr, nullptr, nullptr, nullptr, param, grad, exp_avg,
+                              exp_avg_sq, step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics,
+                              workspace, apply, stream, diag, target_kl);
+}
 
 int64_t pc_ppo_epoch_state_floats(int D, int H, int A) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)

@@ -103,10 +103,27 @@ class PPOConfig:
                                            # (buffer.py:53-61), which gymnasium's same-step auto-reset made V(reset observation); "final_obs" =
                                            # V(the observation the truncated step returned): the rollout keeps it in Buffer.final_obs_buf,
                                            # one value pass per slot (bootstrap_value's arithmetic), then pc_gae_bootstrap
+    update_diagnostics: bool = False       # run_epoch adds losses/approx_kl, losses/clipfrac (means over the minibatch steps evaluated), losses/
+                                           # explained_variance and charts/update_steps: taken inside the update kernels from the logratio and
+                                           # ratio they already form (the *_diag entry points, include/ppocar.h), and one reduction over val / ret
+    target_kl: float | None = None         # Stable-Baselines3's early stop: a minibatch step whose approx_kl > 1.5 * target_kl is not applied and
+                                           # ends the epoch's update (a flag on the device: the captured epoch graph is replayed as it is).
+                                           # Setting it switches update_diagnostics on.  Not with deferred_adam, force_collective or several ranks
 
     def __post_init__(self):
         if self.truncation_bootstrap not in ("reference", "final_obs"):
             raise ValueError(f"PPOConfig.truncation_bootstrap must be 'reference' or 'final_obs', not {self.truncation_bootstrap!r}")
+        if self.target_kl is not None:
+            if isinstance(self.target_kl, bool) or not isinstance(self.target_kl, (int, float)) or not self.target_kl > 0.0:
+                raise ValueError(f"PPOConfig.target_kl must be a positive number or None, not {self.target_kl!r}")
+            self.target_kl = float(self.target_kl)
+            self.update_diagnostics = True
+        if self.update_diagnostics and self.deferred_adam:
+            raise ValueError("PPOConfig.update_diagnostics / target_kl cannot be combined with deferred_adam (the clip + Adam step lives "
+                             "inside the next forward / backward launch there)")
+        if self.update_diagnostics and self.force_collective:
+            raise ValueError("PPOConfig.update_diagnostics / target_kl cannot be combined with force_collective (the multi-rank update "
+                             "path: the ranks would have to agree on the stop)")
 
 
 def flatten_parameters(module):
@@ -224,10 +241,15 @@ class P2PExchange:
             self._h = None
 
 
-def ppo_loss(agent, obs, act, old_logprob, adv, ret, clip_ratio, vf_coef, ent_coef):
-    """One minibatch of train.py:233-255.  `adv` is the raw advantage slice; normalisation is here."""
+def ppo_loss(agent, obs, act, old_logprob, adv, ret, clip_ratio, vf_coef, ent_coef, diagnostics=False):
+    """One minibatch of train.py:233-255.  `adv` is the raw advantage slice; normalisation is here.
+    diagnostics: two more values, (approx_kl, clipfrac) = (mean((ratio - 1) - logratio), mean(|ratio - 1| > clip_ratio)), detached."""
     _, new_logprobs, entropies, new_values = agent.get_action_and_value(obs, act)
     ratios = torch.exp(new_logprobs - old_logprob)                                            # :235
+    if diagnostics:
+        with torch.no_grad():
+            approx_kl = ((ratios - 1.0) - (new_logprobs - old_logprob)).mean()
+            clipfrac = ((ratios - 1.0).abs() > clip_ratio).float().mean()
     adv = (adv - adv.mean()) / adv.std().clamp_min(1e-5)      # :238-240 torch.max(std, 1e-5), without the H2D scalar copy
     policy_loss1 = -adv * ratios                                                              # :243
     policy_loss2 = -adv * torch.clamp(ratios, 1.0 - clip_ratio, 1.0 + clip_ratio)             # :244
@@ -235,7 +257,17 @@ def ppo_loss(agent, obs, act, old_logprob, adv, ret, clip_ratio, vf_coef, ent_co
     value_loss = 0.5 * ((new_values.view(-1) - ret) ** 2).mean()                              # :248-249
     entropy = entropies.mean()                                                                # :252
     loss = policy_loss + vf_coef * value_loss - ent_coef * entropy                            # :255
+    if diagnostics:
+        return loss, policy_loss, value_loss, entropy, approx_kl, clipfrac
     return loss, policy_loss, value_loss, entropy
+
+
+def diag_scalars(diag, explained_variance, into):
+    """The rows of PPOConfig.update_diagnostics from the device block (include/ppocar.h, PC_DIAG_FLOATS) and the variance pass."""
+    n = max(diag[2], 1.0)
+    into.update({"losses/approx_kl": diag[0] / n, "losses/clipfrac": diag[1] / n, "losses/explained_variance": explained_variance,
+                 "charts/update_steps": int(diag[3])})
+    return into
 
 
 class PPOLearner:
@@ -250,12 +282,19 @@ class PPOLearner:
 
     def __init__(self, agent, cfg: PPOConfig, device, rank=0, world_size=1):
         self.agent, self.cfg, self.device, self.rank, self.world_size = agent, cfg, torch.device(device), rank, world_size
+        if cfg.update_diagnostics and world_size > 1:
+            raise ValueError("PPOConfig.update_diagnostics / target_kl need a single rank (the ranks would have to agree on the stop)")
         self.flat_param, self.flat_grad = flatten_parameters(agent)
         if world_size > 1:
             import torch.distributed as dist
             dist.broadcast(self.flat_param, src=0)       # every rank starts from rank 0's parameters
         self.exchange = GradExchange(self.flat_grad, world_size)
         self.collective = world_size > 1 or bool(cfg.force_collective)     # the update has an exchange step
+        self.diag_on = bool(cfg.update_diagnostics)
+        # the block the *_diag kernels keep (PC_DIAG_FLOATS; the torch path books the same numbers), zeroed at the head of every epoch
+        self.diag = torch.zeros(_capi.PC_DIAG_FLOATS, device=self.device) if self.diag_on else None
+        self.target_kl = float(cfg.target_kl) if cfg.target_kl is not None else 0.0
+        self._kl_stop = float(np.float32(1.5 * self.target_kl))            # the kernels' float threshold; 0 = never stop
         if cfg.bootstrap_value not in ("kernel", "fp32"):
             raise ValueError(f"PPOConfig.bootstrap_value must be 'kernel' or 'fp32', not {cfg.bootstrap_value!r}")
         if cfg.exchange not in ("rccl", "p2p"):
@@ -283,7 +322,8 @@ class PPOLearner:
         self.custom = (self.fused and bool(cfg.custom_mlp) and agent._std_mlp() and a1.out_features == 256
                        and lib.pc_ppo_workspace_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features) > 0)
         if self.custom:
-            self._ws = torch.empty(lib.pc_ppo_workspace_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features),
+            ws_floats = lib.pc_ppo_diag_workspace_floats if self.diag_on else lib.pc_ppo_workspace_floats
+            self._ws = torch.empty(ws_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features),
                                    device=self.device, dtype=torch.float32)
         self._epoch_graph = None
         if self.graphs:   # capturable Adam: step count and lr live on the device, so a captured step stays valid
@@ -332,19 +372,25 @@ class PPOLearner:
                                 f["adv"].data_ptr(), f["ret"].data_ptr(), st), "pc_ppo_gather")
         logits = self.agent.actor(f["obs"])
         values = self.agent.critic(f["obs"])
-        check(lib.pc_ppo_loss(di, logits.data_ptr(), values.data_ptr(), f["act"].data_ptr(), f["lp"].data_ptr(),
-                              f["adv"].data_ptr(), f["ret"].data_ptr(), B, logits.shape[1], cfg.clip_ratio, cfg.vf_coef,
-                              cfg.ent_coef, f["dlogits"].data_ptr(), f["dvalues"].data_ptr(), self.metrics.data_ptr(), st),
-              "pc_ppo_loss")
+        loss_args = (di, logits.data_ptr(), values.data_ptr(), f["act"].data_ptr(), f["lp"].data_ptr(), f["adv"].data_ptr(),
+                     f["ret"].data_ptr(), B, logits.shape[1], cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, f["dlogits"].data_ptr(),
+                     f["dvalues"].data_ptr(), self.metrics.data_ptr())
+        if self.diag_on:
+            check(lib.pc_ppo_loss_diag(*loss_args, self.diag.data_ptr(), self.target_kl, st), "pc_ppo_loss_diag")
+        else:
+            check(lib.pc_ppo_loss(*loss_args, st), "pc_ppo_loss")
         self.flat_grad.zero_()
         torch.autograd.backward([logits, values], [f["dlogits"], f["dvalues"]])
 
     def _fused_apply(self):
         cfg = self.cfg
-        check(lib.pc_clip_adam(self._dev_index(), self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                               self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(),
-                               self.flat_param.numel(), cfg.max_grad_norm, 1.0 / self.world_size, 0.9, 0.999, 1e-5,
-                               self._stream()), "pc_clip_adam")
+        args = (self._dev_index(), self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(), self.flat_param.numel(),
+                cfg.max_grad_norm, 1.0 / self.world_size, 0.9, 0.999, 1e-5)
+        if self.diag_on:      # (returns at once when the stop flag is up)
+            check(lib.pc_clip_adam_diag(*args, self.diag.data_ptr(), self._stream()), "pc_clip_adam_diag")
+        else:
+            check(lib.pc_clip_adam(*args, self._stream()), "pc_clip_adam")
 
     def _exchange_and_average(self):
         """GradExchange's contract (flat_grad := the MEAN over ranks) on top of the configured transport."""
@@ -379,12 +425,16 @@ class PPOLearner:
         """pc_ppo_minibatch: gather + forward + loss + backward (+ clip + Adam when single-rank) with no library GEMM."""
         cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
         single = not self.collective
-        check(lib.pc_ppo_minibatch(self._dev_index(), idx.data_ptr(), cfg.batch_size, a1.in_features, a1.out_features, a2.out_features,
-                                   obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                   self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                   self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(), cfg.clip_ratio,
-                                   cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
-                                   self._ws.data_ptr(), 1 if single else 2, self._stream()), "pc_ppo_minibatch")
+        args = (self._dev_index(), idx.data_ptr(), cfg.batch_size, a1.in_features, a1.out_features, a2.out_features,
+                obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(), cfg.clip_ratio,
+                cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
+                self._ws.data_ptr(), 1 if single else 2)
+        if self.diag_on:
+            check(lib.pc_ppo_minibatch_diag(*args, self.diag.data_ptr(), self.target_kl, self._stream()), "pc_ppo_minibatch_diag")
+        else:
+            check(lib.pc_ppo_minibatch(*args, self._stream()), "pc_ppo_minibatch")
         if not single:
             self._sum_gradients()
             self._custom_apply()
@@ -415,12 +465,16 @@ class PPOLearner:
         """pc_ppo_minibatch_prepared on block m of the prepared epoch (+ all-reduce and clip/Adam when multi-rank)."""
         cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
         single = not self.collective
-        check(lib.pc_ppo_minibatch_prepared(self._dev_index(), self._prep.data_ptr() + 4 * m * pf, cfg.batch_size, a1.in_features,
-                                            a1.out_features, a2.out_features, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                                            self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
-                                            self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
-                                            0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr(), 1 if single else 2,
-                                            self._stream()), "pc_ppo_minibatch_prepared")
+        args = (self._dev_index(), self._prep.data_ptr() + 4 * m * pf, cfg.batch_size, a1.in_features,
+                a1.out_features, a2.out_features, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
+                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
+                self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
+                0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr(), 1 if single else 2)
+        if self.diag_on:
+            check(lib.pc_ppo_minibatch_prepared_diag(*args, self.diag.data_ptr(), self.target_kl, self._stream()),
+                  "pc_ppo_minibatch_prepared_diag")
+        else:
+            check(lib.pc_ppo_minibatch_prepared(*args, self._stream()), "pc_ppo_minibatch_prepared")
         if not single:
             self._sum_gradients()
             self._custom_apply()
@@ -447,6 +501,8 @@ class PPOLearner:
         """All minibatch steps of one epoch's update (train.py:223-261) with the hand-written kernels."""
         cfg = self.cfg
         B = cfg.batch_size
+        if self.diag_on:
+            self.diag.zero_()      # sums and stop flag, at the head of every epoch and INSIDE the captured graph: a replay starts unstopped
         if cfg.prepared_minibatches:
             pf = self.prepare_minibatches(idx_all, n_mb, *args)
             if cfg.deferred_adam and not self.collective:
@@ -524,10 +580,27 @@ class PPOLearner:
     # ---- one minibatch, in the two halves the all-reduce separates ---------------------------------------
     def _fwd_bwd(self, obs, act, logprob, adv, ret):
         cfg = self.cfg
-        loss, pl, vl, ent = ppo_loss(self.agent, obs, act, logprob, adv, ret, cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef)
+        loss, pl, vl, ent, *dg = ppo_loss(self.agent, obs, act, logprob, adv, ret, cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef,
+                                          diagnostics=self.diag_on)
         self.flat_grad.zero_()                                                           # train.py:258
         loss.backward()                                                                  # :259
+        if self.diag_on:
+            self._diag_terms = torch.stack(dg).to(torch.float32)                         # (approx_kl, clipfrac) of this minibatch
         return torch.stack([pl.detach(), vl.detach(), ent.detach(), loss.detach()])
+
+    def _book_diag(self):
+        """The torch path's restatement of what the *_diag kernels do with a step's (approx_kl, clipfrac): book it in the block and
+        decide (on the host: this path synchronises) whether the step is applied.  False = the stop: the caller applies nothing and
+        runs no further minibatch of this epoch."""
+        kl, cf = self._diag_terms[0], self._diag_terms[1]
+        stop = self._kl_stop > 0.0 and bool(kl > self._kl_stop)                          # float32 against the float32 threshold
+        with torch.no_grad():
+            self.diag[0] += kl
+            self.diag[1] += cf
+            self.diag[2] += 1.0
+            self.diag[5] = kl
+            self.diag[4 if stop else 3] += 1.0
+        return not stop
 
     def _apply(self, terms):
         nn.utils.clip_grad_norm_(self.agent.parameters(), self.cfg.max_grad_norm)        # train.py:260
@@ -537,8 +610,11 @@ class PPOLearner:
 
     def minibatch_step(self, obs, act, logprob, adv, ret):
         terms = self._fwd_bwd(obs, act, logprob, adv, ret)
+        if self.diag_on and not self._book_diag():
+            return False                               # target_kl: this gradient is not applied, the epoch's update ends here
         self.exchange()                                # the one all-reduce per minibatch
         self._apply(terms)
+        return True
 
     # ---- HIP-graph form ------------------------------------------------------------------------------------
     def _build_graphs(self, obs, act, logprob, adv, ret):
@@ -565,6 +641,9 @@ class PPOLearner:
         # state is SAVED before and RESTORED after, so the graphs can be (re)built at any time -- also on a Trainer whose
         # state was just loaded from a checkpoint (train.py --resume), where the state is not "never stepped".
         saved_param, saved_metrics = self.flat_param.clone(), self.metrics.clone()
+        saved_diag = self.diag.clone() if self.diag_on else None
+        if self.diag_on:
+            self.diag.zero_()                 # (the warm-up steps run, whatever an earlier epoch left in the flag)
         if self.fused:
             saved_opt = {k: getattr(self, k).clone() for k in ("exp_avg", "exp_avg_sq", "step_count", "lr_dev")}
         else:
@@ -596,6 +675,8 @@ class PPOLearner:
             self.optimizer.param_groups[0]["lr"].copy_(saved_lr)
         self.flat_param.copy_(saved_param)
         self.metrics.copy_(saved_metrics)
+        if self.diag_on:
+            self.diag.copy_(saved_diag)
         self._graph_a, self._graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         single = self.world_size == 1
         with torch.cuda.graph(self._graph_a):
@@ -648,14 +729,18 @@ class PPOLearner:
             self._opt_started = True
             self.lr_dev.mul_(cfg.learning_rate_decay)                                    # StepLR(step_size=1), :147,:269
             return
-        use_graph = self.graphs and full
+        # the torch-op step decides the stop on the host between its two halves: not from inside one captured graph
+        use_graph = self.graphs and full and not (self.diag_on and not self.fused)
+        if self.diag_on:
+            self.diag.zero_()
+        stopped = False
         if use_graph and self._graph_key != (obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(),
                                              ret.data_ptr(), M):
             self._build_graphs(obs, act, logprob, adv, ret)
         for it in range(cfg.train_iters):                                                # :223
             for mb in range(n_mb):                                                       # :228
                 idx = idx_all[it, mb * B:(mb + 1) * B]
-                if idx.numel() == 0:
+                if idx.numel() == 0 or stopped:
                     continue
                 if use_graph:
                     self._g_idx.copy_(idx)
@@ -669,7 +754,7 @@ class PPOLearner:
                 elif self.fused and full:
                     self.fused_minibatch_step(idx, obs, act, logprob, adv, ret)
                 else:
-                    self.minibatch_step(obs[idx], act[idx], logprob[idx], adv[idx], ret[idx])
+                    stopped = self.minibatch_step(obs[idx], act[idx], logprob[idx], adv[idx], ret[idx]) is False
         self._opt_started = True
         if self.fused:
             self.lr_dev.mul_(cfg.learning_rate_decay)                                    # StepLR(step_size=1), :147,:269
@@ -733,6 +818,10 @@ class Trainer:
         self.rollout_mode = None
         self.mega_events = None      # bench.py: list of (start, end) events around each pc_rollout launch
         self.episodes = EpisodeStats(N, cfg.reward_scaling, self.device) if cfg.episode_stats else None   # carry 0: the envs were just reset
+        self._ev_out = None          # update_diagnostics: (mean, M2) of ret and of ret - val, explained variance (pc_explained_variance), float64 [5]
+        if cfg.update_diagnostics:
+            self._ev_out = torch.zeros(5, dtype=torch.float64, device=self.device)
+            self._ev_ws = torch.empty(lib.pc_explained_variance_workspace_doubles(self.device.index), dtype=torch.float64, device=self.device)
         self.final_obs = cfg.truncation_bootstrap == "final_obs"
         if self.final_obs:      # the side buffers of one rollout, and the per-step paths' pre-reset rows (pc_env_step's final_obs)
             self.buffer.final_buffers()
@@ -881,6 +970,10 @@ class Trainer:
             adv, ret = buf.calculate_advantages(next_values, self.next_term.reshape(1, -1),
                                                 self.next_trunc.reshape(1, -1), episodes=self.episodes,
                                                 final_values=final_values)   # :203
+            if self._ev_out is not None:      # how much of the returns the critic that ran the rollout explains: before the first minibatch
+                check(lib.pc_explained_variance(self.device.index, buf.val_buf.data_ptr(), ret.data_ptr(), ret.numel(), self._ev_ws.data_ptr(),
+                                                self._ev_out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                      "pc_explained_variance")
         obs, act, _val, logprob = buf.get()                                                      # :206
         self.learner.update(obs.view(-1, *self.obs_dim), act.view(-1), logprob.view(-1), adv.view(-1), ret.view(-1))
         self._aux_valid = False     # the in-kernel bootstrap values belong to THAT rollout and THOSE parameters only
@@ -915,7 +1008,9 @@ class Trainer:
                 rng = getattr(self.agent, "_range_dev", None)      # the fp16x2 domain's status word of the last pack (it may have run inside a graph)
                 rng = rng.to(torch.float32) if rng is not None else torch.zeros(1, device=self.device)
                 dev = torch.cat([L.metrics / self.cfg.train_iters, rew_mean.reshape(1).to(torch.float32), lr, rng])
-            host = torch.empty(7, dtype=torch.float32, pin_memory=True)
+                if L.diag_on:       # the diagnostics block and the explained variance behind the seven floats
+                    dev = torch.cat([dev, L.diag, self._ev_out[4:5].to(torch.float32)])
+            host = torch.empty(dev.numel(), dtype=torch.float32, pin_memory=True)
             host.copy_(dev, non_blocking=True)
             host_ep = None
             if ep_tot is not None:      # the episode totals in float64, next to the seven floats
@@ -948,6 +1043,8 @@ class Trainer:
                "elapsed": elapsed}
         if ep_tot is not None:
             out.update(episode_scalars(ep_tot.tolist(), self.cfg.reward_scaling))
+        if self.learner.diag_on:
+            diag_scalars(self.learner.diag.tolist(), float(self._ev_out[4].to(torch.float32)), out)
         return out
 
     def flush_scalars(self):
@@ -967,6 +1064,8 @@ class Trainer:
                "charts/SPS": gstep / max(elapsed, 1e-9), "global_step": gstep, "elapsed": elapsed}
         if host_ep is not None:
             out.update(episode_scalars(host_ep.tolist(), self.cfg.reward_scaling))
+        if len(m) > 7:
+            diag_scalars(m[7:7 + _capi.PC_DIAG_FLOATS], m[7 + _capi.PC_DIAG_FLOATS], out)
         return out
 
     # ---- checkpoint / resume (the reference only saves agent.state_dict(), train.py:283,301) ----

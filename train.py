@@ -58,6 +58,10 @@ def parse_args(argv=None):
     p.add_argument("--truncation-bootstrap", default="reference", choices=["reference", "final_obs"],
                    help="GAE's next value at a time-limit truncation: the reference's val_buf[t + 1] (the reset observation's value after "
                    "the auto-reset), or the value of the observation the truncated step returned")
+    p.add_argument("--update-diagnostics", action="store_true", help="print and log what the update did: losses/approx_kl, losses/clipfrac, "
+                   "losses/explained_variance, charts/update_steps")
+    p.add_argument("--target-kl", type=float, default=None, help="stop an epoch's update at the first minibatch step whose approx_kl exceeds "
+                   "1.5 x this (Stable-Baselines3's target_kl; implies --update-diagnostics)")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -100,7 +104,8 @@ def main(argv=None):
                     reward_scaling=args.reward_scaling, track=args.track, num_rays=args.num_rays, env_dtype=args.env_dtype,
                     seed=args.seed, full_sweep=args.full_sweep, bootstrap_value=args.bootstrap_value,
                     policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range,
-                    episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap)
+                    episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap,
+                    update_diagnostics=args.update_diagnostics, target_kl=args.target_kl)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
@@ -118,6 +123,9 @@ def main(argv=None):
                 ret = scalars["charts/episodic_return"]
                 line += (f"Episodes: {scalars['charts/episodes']}, return {ret:.3f}, length {scalars['charts/episodic_length']:.1f}, "
                          f"laps {scalars['charts/laps_per_episode']:.3f}. " if ret is not None else "Episodes: 0. ")
+            if "losses/approx_kl" in scalars:
+                line += (f"KL {scalars['losses/approx_kl']:.5f}, clipfrac {scalars['losses/clipfrac']:.3f}, explained variance "
+                         f"{scalars['losses/explained_variance']:.3f}, {scalars['charts/update_steps']} update steps. ")
             print(line, flush=True)
             log.write(json.dumps(scalars) + "\n")
             log.flush()
