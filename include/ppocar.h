@@ -223,7 +223,18 @@ int pc_gae_bootstrap(int device, const float* rew, const float* val, const float
  * draw action ~ Categorical(logits) and return log_prob(action) and (optionally) the entropy.
  * Counter-based RNG (Philox-4x32-10) keyed by (seed, offset): the same (seed, offset, N, A)
  * gives the same actions on any launch geometry.  actions [N] int64, logprob/entropy [N] float32
- * (entropy may be NULL).  All device. */
+ * (entropy may be NULL).  All device.  A <= 16, else PC_ERR_UNSUPPORTED.
+ * THE STREAM (a contract: pc_sample, pc_policy_act and pc_rollout draw from it alike; tests/draw_reference.py is its plain
+ * reference and tests/test_policy_draw_*.py hold the kernels to it element by element).  Draw number `offset` of element idx (the
+ * element's position in THAT call, 0 .. N - 1; both 64-bit) is
+ *   block   = Philox-4x32-10 (Salmon et al., Random123: multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85) of
+ *             counter = (idx low 32 bits, idx high, (offset >> 2) low, (offset >> 2) high), key = (seed low, seed high)
+ *   x       = word (offset & 3) of the block: four consecutive offsets of an element share one block
+ *   u       = min(((float)(x >> 8) + 0.5f) * 2^-24, 1 - 2^-24) in float32: strictly inside (0, 1).  (k + 0.5 is rounded to float32
+ *             for k >= 2^23; without the bound k = 2^24 - 1 gave 1.0f.)
+ *   action  = the number of bins i < A - 1 of the float32 inclusive CDF of softmax(logits) with u >= cdf_i: the draw of an element
+ *             depends on its logits and (seed, offset, idx), nothing else.  The last bin absorbs the rounding of the float32 CDF's
+ *             end (a few ulp below 1): a last action of probability 0 can be drawn only by a u within 2e-6 of 1. */
 int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, uint64_t offset, int64_t* actions,
               float* logprob, float* entropy, void* stream);
 

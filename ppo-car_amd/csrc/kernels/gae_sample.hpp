@@ -246,7 +246,15 @@ __device__ __forceinline__ PhiloxBlock philox_block(uint64_t seed, uint64_t bloc
 }
 __device__ __forceinline__ float philox_word_uniform(const PhiloxBlock& b, const unsigned word) {  // word: wave-uniform
     const uint32_t x = word == 0 ? b.w[0] : word == 1 ? b.w[1] : word == 2 ? b.w[2] : b.w[3];
-    return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1) open, 24 bits
+    // (0, 1) open, from the word's top 24 bits k: u = ((float)k + 0.5f) * 2^-24 in float32 (include/ppocar.h states it so).  k + 0.5 is
+    // not a float32 from k = 2^23 on (it rounds to even), and for k = 2^24 - 1 it rounds UP to 2^24: unbounded, that one word in 2^24
+    // gave u == 1.0f, which passes every bin of the inverse CDF and returned the last action whatever its probability.  The bound is
+    // the largest float32 below 1; it changes that word's uniform and no other, so every other draw of every seeded run keeps its bits.
+    // Written as ONE fused multiply-add -- fma(k, 2^-24, 2^-25) rounds the exact (k + 0.5) 2^-24 once, and scaling by a power of two
+    // commutes with rounding: the same bits as add-then-multiply for every k (tests/test_policy_draw_host.py walks all 2^24) -- so
+    // that convert, fma, min are the three instructions convert, add, multiply were: with the minimum appended to the old pair the
+    // persistent rollout launch measured 2.5 % slower, in this form it equals the parent (profiles/uniform_bound_ab.txt).
+    return fminf(__builtin_fmaf((float)(x >> 8), 1.0f / 16777216.0f, 1.0f / 33554432.0f), 0x1.fffffep-1f);
 }
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, uint64_t idx) {
     return philox_word_uniform(philox_block(seed, offset >> 2, idx), (unsigned)(offset & 3));
