@@ -437,6 +437,39 @@ int pc_clip_adam_diag(int device, float* param, float* grad, float* exp_avg, flo
 int64_t pc_explained_variance_workspace_doubles(int device);
 int pc_explained_variance(int device, const float* val, const float* ret, int64_t M, double* workspace, double* out, void* stream);
 
+/* ---- the same minibatch step for LARGE minibatches, 1024 < B <= PC_PPO_LARGE_MAX_B (opt-in: the entry points above are untouched
+ * and keep their limit).  No library GEMM, no atomics, float32 arithmetic throughout (the advantage statistics accumulate in
+ * float64 and are rounded once), every index -> row address in 64 bits.
+ * pc_ppo_adv_stats: for each of n_mb minibatches (minibatch m reads its B indices at idx[m * idx_ld ...]) the pair
+ *   stats[m][0..1] = (mean, max(unbiased std, 1e-5)) of adv[idx] (train.py:238-240): float64 sums about a shift taken from the
+ *   data, several workgroups per minibatch and a merge in a fixed order, two launches.  It depends on idx and adv only, so one call at
+ *   the head of an epoch covers every minibatch of it.  workspace: pc_ppo_adv_stats_workspace_doubles(n_mb, B) doubles.
+ *   NULL arrays, n_mb < 1 or > 65535, idx_ld < B: PC_ERR_INVALID_ARG, checked before any device call.
+ * pc_ppo_minibatch_large: pc_ppo_minibatch's arguments, contract (apply 0 / 1 / 2, metrics, step_count, lr_dev), status codes and
+ *   order of checks, plus adv_stats = this minibatch's pair from pc_ppo_adv_stats (device memory).  The forward / backward launch
+ *   is a FIXED grid of pc_ppo_large_parts(device, B) = min(ceil(B / 8), compute units of the device) workgroups: workgroup g loads the
+ *   parameters once and walks the groups of 8 samples g, g + G, g + 2 G, ... with its gradient accumulators in registers, then
+ *   writes one partial; the partials are summed in index order by the gradient-reduction launch of pc_ppo_minibatch, and the clip +
+ *   Adam launch is the same one.  The summation order is fixed for a given (device, B): two calls give the same bits; it is NOT the
+ *   order of pc_ppo_minibatch, and it differs between devices with different compute-unit counts.
+ *   workspace: pc_ppo_large_workspace_floats(device, B, D, H, A) floats, laid out as pc_ppo_minibatch's with `parts` partials:
+ *   [parts][n_pad] gradient partials (n_pad = the parameter count rounded up to 4), [parts][4] metric partials, then the
+ *   per-block squared-norm partials.  Nothing is read that the step has not written: the buffer needs no initialisation.
+ *   Never synchronises; every launch goes to `stream`.
+ * PC_ERR_UNSUPPORTED unless H == 256, 1 <= A <= 15, 1 <= D <= 40, 1024 < B <= PC_PPO_LARGE_MAX_B; PC_ERR_NO_DEVICE for device < 0
+ * or a device the runtime does not know (the grid depends on the device). */
+#define PC_PPO_LARGE_MAX_B (1 << 20)
+int64_t pc_ppo_large_workspace_floats(int device, int B, int D, int H, int A);
+int pc_ppo_large_parts(int device, int B);
+int64_t pc_ppo_adv_stats_workspace_doubles(int n_mb, int B);
+int pc_ppo_adv_stats(int device, const int64_t* idx, int64_t idx_ld, int n_mb, int B, const float* adv, float* stats, double* workspace,
+                     void* stream);
+int pc_ppo_minibatch_large(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
+                           const float* old_logprob, const float* adv, const float* ret, const float* adv_stats, float* param, float* grad,
+                           float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef,
+                           double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace,
+                           int apply, void* stream);
+
 /* The whole minibatch loop of one epoch (train.py:223-261) over n_mb prepared minibatches (consecutive blocks of
  * pc_ppo_prepared_floats(B, D) floats at `prepared`), with the clip + Adam step of minibatch i taken by the forward / backward
  * launch of minibatch i + 1 as it loads the parameters (every workgroup needs all of them anyway; workgroup 0 writes the new

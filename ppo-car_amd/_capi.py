@@ -18,6 +18,7 @@ PC_XCHG_HANDLE_BYTES = 128
 PC_DTYPE_F32, PC_DTYPE_F64 = 0, 1
 PC_EPISODE_BUFFER, PC_EPISODE_STEPS = 0, 1
 PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppocar.h)
+PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_TIME_LIMIT = 1000     # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
 PC_OPT_ROLLOUT_FORM, PC_OPT_ROLLOUT_EPW, PC_OPT_ROLLOUT_FAST = 1, 2, 3
 PC_KERNEL_NAMES = {0: "none", 1: "K9", 2: "K9s", 3: "K9-literal", 4: "K9d-filter", 5: "K9s-literal", 6: "K9d-selector", 7: "K9m", 8: "K9m-literal"}     # pc_env_last_rollout_kernel
@@ -106,6 +107,11 @@ _sig = {
     "pc_ppo_epoch_state_floats": (_i64, [_i, _i, _i]),
     "pc_ppo_epoch_prepared": (_i, [_i, _vp, _i, _i, _i, _i, _i] + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _vp, _vp]),
     "pc_ppo_minibatch": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 5 + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp]),
+    "pc_ppo_large_workspace_floats": (_i64, [_i, _i, _i, _i, _i]),
+    "pc_ppo_large_parts": (_i, [_i, _i]),
+    "pc_ppo_adv_stats_workspace_doubles": (_i64, [_i, _i]),
+    "pc_ppo_adv_stats": (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "pc_ppo_minibatch_large": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 5 + [_vp] + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp]),
     "pc_ppo_diag_workspace_floats": (_i64, [_i, _i, _i, _i]),
     "pc_ppo_minibatch_diag": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 5 + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp, _d, _vp]),
     "pc_ppo_minibatch_prepared_diag": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp, _d, _vp]),

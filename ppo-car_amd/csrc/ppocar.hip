@@ -77,6 +77,7 @@
 #include "kernels/rollout.hpp"
 #include "kernels/env_steps.hpp"
 #include "kernels/update.hpp"
+#include "kernels/update_large.hpp"
 #include "kernels/diagnostics.hpp"
 #include "kernels/exchange.hpp"
 
@@ -1851,9 +1852,9 @@ int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
 struct MbPlan {
     int n_param, n_part, n_blk, n_pad, HD, mid_end;
     float *partial, *metric_partial, *norm_partial, *diag_partial;
-    MbPlan(int B, int D, int H, int A, float* workspace) {
+    MbPlan(int B, int D, int H, int A, float* workspace, int parts = 0) {      // parts > 0: K10L's fixed grid (pc_ppo_large_parts)
         n_param = 2 * (H * D + H) + A * H + A + H + 1;
-        n_part = (B + FB_S - 1) / FB_S;
+        n_part = parts > 0 ? parts : (B + FB_S - 1) / FB_S;
         n_blk = (n_param + 255) / 256;
         n_pad = (n_param + 3) & ~3;          // a partial's row stride: 16-byte aligned rows
         HD = H * D;
@@ -2004,6 +2005,94 @@ int pc_ppo_minibatch_prepared_diag(int device, const float* prepared_mb, int B, 
     return ppo_minibatch_impl(device, nullptr, prepared_mb, B, D, H, A, nullptr, nullptr, nullptr, nullptr, nullptr, param, grad, exp_avg,
                               exp_avg_sq, step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics,
                               workspace, apply, stream, diag, target_kl);
+}
+
+// ---- the large-minibatch step (kernels/update_large.hpp): 1024 < B <= PC_PPO_LARGE_MAX_B
+static bool large_shape(int B, int D, int H, int A) {
+    return H == 256 && A >= 1 && A <= 15 && D >= 1 && D <= 40 && B > 1024 && B <= PC_PPO_LARGE_MAX_B;
+}
+// K10L's grid = its number of partials: one workgroup per group of 8 samples up to one per compute unit.  The ONE expression the
+// workspace size, the launch and pc_ppo_large_parts share.
+static int large_parts(int device, int B, int* out) {
+    if (device < 0) return PC_ERR_NO_DEVICE;
+    int cus = 0;
+    if (device_cus(device, &cus) != PC_OK) return PC_ERR_NO_DEVICE;
+    *out = std::min((B + FB_S - 1) / FB_S, cus);
+    return PC_OK;
+}
+
+int pc_ppo_large_parts(int device, int B) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (B <= 1024 || B > PC_PPO_LARGE_MAX_B) return PC_ERR_UNSUPPORTED;
+    int parts = 0;
+    const int rc = large_parts(device, B, &parts);
+    return rc != PC_OK ? rc : parts;
+}
+
+int64_t pc_ppo_large_workspace_floats(int device, int B, int D, int H, int A) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!large_shape(B, D, H, A)) return PC_ERR_UNSUPPORTED;
+    int parts = 0;
+    const int rc = large_parts(device, B, &parts);
+    if (rc != PC_OK) return rc;
+    const int64_t n_param = 2 * ((int64_t)H * D + H) + (int64_t)A * H + A + H + 1;
+    return parts * ((n_param + 3) & ~(int64_t)3) + parts * 4 + (n_param + 255) / 256;      // (MbPlan's layout with n_part = parts)
+}
+
+int64_t pc_ppo_adv_stats_workspace_doubles(int n_mb, int B) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (n_mb < 1) return PC_ERR_INVALID_ARG;
+    if (B <= 1024 || B > PC_PPO_LARGE_MAX_B) return PC_ERR_UNSUPPORTED;
+    return (int64_t)n_mb * adv_stats_parts(B) * 2;
+}
+
+int pc_ppo_adv_stats(int device, const int64_t* idx, int64_t idx_ld, int n_mb, int B, const float* adv, float* stats, double* workspace,
+                     void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!idx || !adv || !stats || !workspace || n_mb < 1 || n_mb > 65535 || idx_ld < B) return PC_ERR_INVALID_ARG;
+    if (B <= 1024 || B > PC_PPO_LARGE_MAX_B) return PC_ERR_UNSUPPORTED;
+    if (device < 0) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int P = adv_stats_parts(B);
+    hipLaunchKernelGGL(ppo_adv_stats_large_kernel, dim3(P, n_mb), dim3(AS_THREADS), 0, (hipStream_t)stream, idx, idx_ld, B, adv, workspace);
+    hipLaunchKernelGGL(ppo_adv_stats_merge_kernel, dim3(n_mb), dim3(64), 0, (hipStream_t)stream, idx, idx_ld, B, P, adv, workspace, stats);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_ppo_minibatch_large(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
+                           const float* old_logprob, const float* adv, const float* ret, const float* adv_stats, float* param, float* grad,
+                           float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio, double vf_coef,
+                           double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace,
+                           int apply, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!param || !grad || !metrics || !workspace) return PC_ERR_INVALID_ARG;
+    if (!idx || !obs || !act || !old_logprob || !adv || !ret || !adv_stats) return PC_ERR_INVALID_ARG;
+    if (apply == 1 && (!exp_avg || !exp_avg_sq || !step_count || !lr_dev)) return PC_ERR_INVALID_ARG;
+    if (apply == 2 && !step_count) return PC_ERR_INVALID_ARG;
+    if (apply < 0 || apply > 2) return PC_ERR_INVALID_ARG;
+    if (!large_shape(B, D, H, A)) return PC_ERR_UNSUPPORTED;
+    int parts = 0;
+    const int rc = large_parts(device, B, &parts);
+    if (rc != PC_OK) return rc;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const MbPlan pl(B, D, H, A, workspace, parts);
+    hipStream_t st = (hipStream_t)stream;
+#define PC_FBL(DM, ACV, DCV)                                                                                                                   \
+    hipLaunchKernelGGL((ppo_fwdbwd_large_kernel<DM, ACV, DCV>), dim3(pl.n_part), dim3(256), 0, st, idx, B, D, A, obs, act, old_logprob, adv, ret, \
+                       adv_stats, param, (float)clip_ratio, (float)vf_coef, (float)ent_coef, pl.partial, pl.metric_partial)
+    if (A == 9 && D == 23) PC_FBL(24, 9, 23);       // (launch_fwdbwd's menu)
+    else if (A == 9 && D == 18) PC_FBL(24, 9, 18);
+    else if (A == 9 && D == 39) PC_FBL(40, 9, 39);
+    else if (D <= 24) PC_FBL(24, 0, 0);
+    else PC_FBL(40, 0, 0);
+#undef PC_FBL
+    launch_reduce(pl, B, vf_coef, ent_coef, grad, metrics, apply ? step_count : nullptr, st);
+    if (apply == 1) launch_adam(pl, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
 }
 
 int64_t pc_ppo_epoch_state_floats(int D, int H, int A) {

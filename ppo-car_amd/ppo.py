@@ -109,6 +109,11 @@ class PPOConfig:
     target_kl: float | None = None         # Stable-Baselines3's early stop: a minibatch step whose approx_kl > 1.5 * target_kl is not applied and
                                            # ends the epoch's update (a flag on the device: the captured epoch graph is replayed as it is).
                                            # Setting it switches update_diagnostics on.  Not with deferred_adam, force_collective or several ranks
+    large_minibatch: bool = False          # opt-in, batch_size > 1024 (where the hand-written step above ends and the torch-op step takes over): the
+                                           # large-minibatch kernels (pc_ppo_adv_stats once per epoch, pc_ppo_minibatch_large per minibatch: a fixed
+                                           # grid of workgroups that walk the samples, no library GEMM).  Needs fused_update, custom_mlp, the standard
+                                           # 256-wide MLPs and full minibatches; not with update_diagnostics / target_kl, deferred_adam or full_sweep.
+                                           # batch_size <= 1024: accepted, changes nothing
 
     def __post_init__(self):
         if self.truncation_bootstrap not in ("reference", "final_obs"):
@@ -124,6 +129,16 @@ class PPOConfig:
         if self.update_diagnostics and self.force_collective:
             raise ValueError("PPOConfig.update_diagnostics / target_kl cannot be combined with force_collective (the multi-rank update "
                              "path: the ranks would have to agree on the stop)")
+        if self.large_minibatch and self.batch_size > 1024:
+            if self.update_diagnostics:
+                raise ValueError("PPOConfig.large_minibatch cannot be combined with update_diagnostics / target_kl (the diagnostics "
+                                 "partials assume at most 128 workgroups)")
+            if self.deferred_adam:
+                raise ValueError("PPOConfig.large_minibatch cannot be combined with deferred_adam (the deferred chain runs on prepared "
+                                 "minibatches of at most 1024 samples)")
+            if self.full_sweep:
+                raise ValueError("PPOConfig.large_minibatch cannot be combined with full_sweep (its indices are drawn on the device, "
+                                 "outside the epoch's index block)")
 
 
 def flatten_parameters(module):
@@ -325,6 +340,25 @@ class PPOLearner:
             ws_floats = lib.pc_ppo_diag_workspace_floats if self.diag_on else lib.pc_ppo_workspace_floats
             self._ws = torch.empty(ws_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features),
                                    device=self.device, dtype=torch.float32)
+        self.n_minibatches = len(range(0, cfg.n_steps, cfg.batch_size))     # train.py:228
+        # the large-minibatch kernels (PPOConfig.large_minibatch): where the path above ends.  Every condition is known here -- a
+        # minibatch is full when the rollout holds n_minibatches * batch_size samples -- so the path never changes between epochs
+        self.large = (bool(cfg.large_minibatch) and cfg.batch_size > 1024 and bool(cfg.fused_update) and bool(cfg.custom_mlp)
+                      and self.device.type == "cuda" and agent._std_mlp() and a1.out_features == 256
+                      and cfg.n_steps * cfg.n_envs >= self.n_minibatches * cfg.batch_size)
+        if self.large:
+            D, A, n_mb_total = a1.in_features, agent.actor[2].out_features, cfg.train_iters * self.n_minibatches
+            ws = lib.pc_ppo_large_workspace_floats(self._dev_index(), cfg.batch_size, D, 256, A)
+            check(min(ws, 0), "pc_ppo_large_workspace_floats")        # (an unsupported shape is an error, not a reason to fall back)
+            self.exp_avg = torch.zeros_like(self.flat_param)
+            self.exp_avg_sq = torch.zeros_like(self.flat_param)
+            self.step_count = torch.zeros(1, device=self.device)
+            self.lr_dev = torch.full((1,), cfg.learning_rate, device=self.device, dtype=torch.float32)
+            self._ws = torch.empty(ws, device=self.device, dtype=torch.float32)
+            self._adv_stats = torch.empty(n_mb_total, 2, device=self.device, dtype=torch.float32)
+            self._adv_stats_ws = torch.empty(lib.pc_ppo_adv_stats_workspace_doubles(n_mb_total, cfg.batch_size), device=self.device,
+                                             dtype=torch.float64)
+        self.flat_adam = self.fused or self.large      # the Adam state is exp_avg / exp_avg_sq / step_count / lr_dev, not a torch optimizer's
         self._epoch_graph = None
         if self.graphs:   # capturable Adam: step count and lr live on the device, so a captured step stays valid
             lr = torch.tensor(cfg.learning_rate, device=self.device, dtype=torch.float32)
@@ -333,7 +367,6 @@ class PPOLearner:
             self.optimizer = torch.optim.Adam(agent.parameters(), lr=cfg.learning_rate, eps=1e-5)        # train.py:146
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=1, gamma=cfg.learning_rate_decay)  # :147
         self._np_rng = np.random.default_rng(cfg.seed * 7919 + rank)
-        self.n_minibatches = len(range(0, cfg.n_steps, cfg.batch_size))     # train.py:228
         idx = torch.empty(cfg.train_iters, self.n_minibatches * cfg.batch_size, dtype=torch.int64)
         # two pinned staging buffers, used alternately: epochs are queued without host synchronisation, so the async
         # H2D copy of epoch k may still be pending when the host draws the indices of epoch k+1
@@ -346,7 +379,7 @@ class PPOLearner:
         self._graph_key = None
 
     def current_lr(self):
-        if self.fused:
+        if self.flat_adam:
             return float(self.lr_dev)
         lr = self.optimizer.param_groups[0]["lr"]
         return float(lr) if torch.is_tensor(lr) else lr
@@ -497,10 +530,37 @@ class PPOLearner:
             self._sum_gradients()     # the 1/W is folded into pc_clip_adam
         self._fused_apply()
 
+    def _large_epoch_body(self, idx_all, n_mb, args):
+        """The epoch's update with the large-minibatch kernels: the advantage statistics of all train_iters x n_mb minibatches in one
+        launch pair, then pc_ppo_minibatch_large per minibatch on its slice of the epoch's index block (+ all-reduce and clip / Adam
+        when there is an exchange step, as custom_minibatch_step)."""
+        cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
+        obs, act, logprob, adv, ret = args
+        B, total = cfg.batch_size, cfg.train_iters * n_mb
+        if not (idx_all.is_contiguous() and idx_all.shape[1] == n_mb * B):
+            raise ValueError("large_minibatch: the epoch's index block must hold train_iters x n_minibatches full minibatches")
+        di, st, single = self._dev_index(), self._stream(), not self.collective
+        check(lib.pc_ppo_adv_stats(di, idx_all.data_ptr(), B, total, B, adv.data_ptr(), self._adv_stats.data_ptr(),
+                                   self._adv_stats_ws.data_ptr(), st), "pc_ppo_adv_stats")
+        for m in range(total):                    # minibatch m = it * n_mb + mb starts at element m * B
+            check(lib.pc_ppo_minibatch_large(di, idx_all.data_ptr() + 8 * m * B, B, a1.in_features, a1.out_features, a2.out_features,
+                                             obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                             self._adv_stats.data_ptr() + 8 * m, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
+                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
+                                             self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
+                                             0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr(), 1 if single else 2, st),
+                  "pc_ppo_minibatch_large")
+            if not single:
+                self._sum_gradients()
+                self._custom_apply()
+
     def _epoch_body(self, idx_all, n_mb, args):
         """All minibatch steps of one epoch's update (train.py:223-261) with the hand-written kernels."""
         cfg = self.cfg
         B = cfg.batch_size
+        if self.large:
+            self._large_epoch_body(idx_all, n_mb, args)
+            return
         if self.diag_on:
             self.diag.zero_()      # sums and stop flag, at the head of every epoch and INSIDE the captured graph: a replay starts unstopped
         if cfg.prepared_minibatches:
@@ -703,7 +763,9 @@ class PPOLearner:
         full = idx_all.shape[1] >= n_mb * B          # every minibatch has exactly B samples
         if self.fused and full and getattr(self, "_f", None) is None:
             self._fused_alloc(obs.shape[1], self.agent.actor[2].out_features)
-        if self.custom and full and not cfg.full_sweep:
+        if self.large and not full:
+            raise ValueError(f"large_minibatch: {M} samples do not fill {n_mb} minibatches of {B}")
+        if (self.custom or self.large) and full and not cfg.full_sweep:
             # three tiny launches per minibatch, indices read in place from the epoch's index block; single rank +
             # graphs: the whole epoch's update (train_iters x n_mb minibatches) is ONE captured graph
             args = (obs, act, logprob, adv, ret)
@@ -711,7 +773,7 @@ class PPOLearner:
                 key = tuple(t.data_ptr() for t in args) + (M, idx_all.data_ptr())
                 if self._epoch_graph is None or self._epoch_key != key:
                     torch.cuda.synchronize(self.device)
-                    if cfg.prepared_minibatches:
+                    if cfg.prepared_minibatches and not self.large:
                         self.prepare_minibatches(idx_all, n_mb, *args)      # (allocates outside the capture)
                         if getattr(self, "_state2", None) is None and cfg.deferred_adam and not self.collective:
                             a1_, a2_ = self.agent.actor[0], self.agent.actor[2]
@@ -1004,7 +1066,7 @@ class Trainer:
             prev = self.flush_scalars()
             L = self.learner
             with torch.no_grad():
-                lr = L.lr_dev.reshape(1).to(torch.float32) if L.fused else torch.full((1,), float(L.current_lr()), device=self.device)
+                lr = L.lr_dev.reshape(1).to(torch.float32) if L.flat_adam else torch.full((1,), float(L.current_lr()), device=self.device)
                 rng = getattr(self.agent, "_range_dev", None)      # the fp16x2 domain's status word of the last pack (it may have run inside a graph)
                 rng = rng.to(torch.float32) if rng is not None else torch.zeros(1, device=self.device)
                 dev = torch.cat([L.metrics / self.cfg.train_iters, rew_mean.reshape(1).to(torch.float32), lr, rng])
@@ -1072,9 +1134,9 @@ class Trainer:
     def state_dict(self):
         """Everything needed to continue a run bit-for-bit: policy, optimizer, lr, env state, RNG counters."""
         L = self.learner
-        opt = ({"exp_avg": L.exp_avg, "exp_avg_sq": L.exp_avg_sq, "step_count": L.step_count, "lr_dev": L.lr_dev} if L.fused
+        opt = ({"exp_avg": L.exp_avg, "exp_avg_sq": L.exp_avg_sq, "step_count": L.step_count, "lr_dev": L.lr_dev} if L.flat_adam
                else {"optimizer": L.optimizer.state_dict(), "scheduler": L.scheduler.state_dict()})
-        return {"agent": self.agent.state_dict(), "opt": opt, "fused": L.fused, "env": self.envs.get_state(),
+        return {"agent": self.agent.state_dict(), "opt": opt, "fused": L.flat_adam, "env": self.envs.get_state(),
                 "next_obs": self.next_obs, "next_term": self.next_term, "next_trunc": self.next_trunc,
                 "rng_base": self.rng_base, "np_rng": L._np_rng.bit_generator.state, "epoch": self.epoch,
                 "global_step_idx": self.global_step_idx, "agent_rng_offset": self.agent._rng_offset,
@@ -1083,14 +1145,14 @@ class Trainer:
 
     def load_state_dict(self, sd):
         L = self.learner
-        if sd["fused"] != L.fused:
+        if sd["fused"] != L.flat_adam:
             raise ValueError("checkpoint was written with a different update path (fused_update)")
         self._aux_valid = False     # bootstrap values / reward totals of an earlier rollout do not belong to the loaded state
         self._rollout_graph = None  # a captured per-step rollout belongs to the state it was captured for (it is re-captured after one eager pass)
         self._eager_rollouts = 0
         with torch.no_grad():
             self.agent.load_state_dict(sd["agent"])        # parameters are views into the flat buffer: copied in place
-            if L.fused:
+            if L.flat_adam:
                 for k in ("exp_avg", "exp_avg_sq", "step_count", "lr_dev"):
                     getattr(L, k).copy_(sd["opt"][k])
             else:

@@ -62,6 +62,8 @@ def parse_args(argv=None):
                    "losses/explained_variance, charts/update_steps")
     p.add_argument("--target-kl", type=float, default=None, help="stop an epoch's update at the first minibatch step whose approx_kl exceeds "
                    "1.5 x this (Stable-Baselines3's target_kl; implies --update-diagnostics)")
+    p.add_argument("--large-minibatch", action="store_true", help="--batch-size above 1024: the hand-written large-minibatch update kernels "
+                   "instead of the torch-op step (PPOConfig.large_minibatch; changes nothing up to 1024)")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -105,7 +107,8 @@ def main(argv=None):
                     seed=args.seed, full_sweep=args.full_sweep, bootstrap_value=args.bootstrap_value,
                     policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range,
                     episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap,
-                    update_diagnostics=args.update_diagnostics, target_kl=args.target_kl)
+                    update_diagnostics=args.update_diagnostics, target_kl=args.target_kl,
+                    large_minibatch=args.large_minibatch)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
