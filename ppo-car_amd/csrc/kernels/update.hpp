@@ -35,78 +35,7 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {  // all threads
     return t;
 }
 
-// K7: clipped-PPO loss of one minibatch, forward AND backward w.r.t. the network outputs (train.py:235-255):
-//   ratio = exp(new_lp - old_lp); A = (adv - mean) / max(std_unbiased, 1e-5)
-//   L_pi = mean(max(-A r, -A clamp(r, 1-c, 1+c))); L_v = 0.5 mean((v - ret)^2); H = mean(entropy)
-//   loss = L_pi + vf L_v - ec H
-// One workgroup, one sample per thread (B <= 1024).  Gradients as autograd produces them:
-//   dloss/dv_i      = vf (v_i - ret_i) / B
-//   dloss/dlp_i     = (1/B) r_i * (-A_i if -A_i r_i >= -A_i clamp(r_i) else 0)     [torch.max / clamp backward]
-//   dloss/dlogit_ik = dloss/dlp_i (1[k = a_i] - p_ik) + (ec/B) p_ik (log p_ik + H_i)
-// metrics[0..3] += (L_pi, L_v, H, loss)  (train.py:263-266).
-template <int AMAX>
-__global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict__ logits, const float* __restrict__ values,
-                                                        const float* __restrict__ act, const float* __restrict__ old_lp,
-                                                        const float* __restrict__ adv, const float* __restrict__ ret, const int B,
-                                                        const int A, const float clip, const float vf, const float ec,
-                                                        float* __restrict__ dlogits, float* __restrict__ dvalues,
-                                                        float* __restrict__ metrics) {
-    __shared__ float sh[16];
-    const int i = threadIdx.x;
-    const bool on = i < B;
-    const float invB = 1.0f / (float)B;
-    const float a_raw = on ? adv[i] : 0.0f;
-    const float mean = block_sum(a_raw, sh) * invB;
-    const float dev = on ? a_raw - mean : 0.0f;
-    const float var = block_sum(dev * dev, sh) / (float)(B - 1);   // unbiased, as Tensor.std() (train.py:239)
-    const float sd = fmaxf(sqrtf(var), 1e-5f);                     // torch.max(std, 1e-5) (train.py:239-240)
-    float pl = 0.0f, vl = 0.0f, ent = 0.0f;
-    if (on) {
-        float l[AMAX];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < AMAX; ++k) {
-            l[k] = k < A ? logits[i * A + k] : -INFINITY;
-            mx = fmaxf(mx, l[k]);
-        }
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < AMAX; ++k) sum += k < A ? expf(l[k] - mx) : 0.0f;
-        const float lse = mx + logf(sum);
-        const int a = (int)act[i];
-        float new_lp = 0.0f;
-        float pk[AMAX], lpk[AMAX];
-#pragma unroll
-        for (int k = 0; k < AMAX; ++k) {
-            lpk[k] = k < A ? l[k] - lse : 0.0f;
-            pk[k] = k < A ? expf(lpk[k]) : 0.0f;
-            ent -= pk[k] * lpk[k];
-            if (k == a) new_lp = lpk[k];
-        }
-        const float r = expf(new_lp - old_lp[i]);                                  // :235
-        const float An = dev / sd;                                                 // :238-240
-        const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
-        const float pl1 = -An * r, pl2 = -An * rc;                                 // :243-244
-        pl = fmaxf(pl1, pl2);                                                      // :245
-        const float dv = values[i] - ret[i];
-        vl = 0.5f * dv * dv;                                                       // :249
-        const float g_lp = (pl1 >= pl2 ? -An : 0.0f) * r * invB;
-        dvalues[i] = vf * dv * invB;
-#pragma unroll
-        for (int k = 0; k < AMAX; ++k)
-            if (k < A) dlogits[i * A + k] = g_lp * ((k == a ? 1.0f : 0.0f) - pk[k]) + ec * invB * pk[k] * (lpk[k] + ent);
-    }
-    const float s_pl = block_sum(pl, sh) * invB, s_vl = block_sum(vl, sh) * invB, s_en = block_sum(ent, sh) * invB;
-    if (i == 0) {
-        metrics[0] += s_pl;
-        metrics[1] += s_vl;
-        metrics[2] += s_en;
-        metrics[3] += s_pl + vf * s_vl - ec * s_en;                                // :255
-    }
-}
-
-
-// Update diagnostics (the *_diag entry points; the plain kernels are untouched).  Per minibatch, from the very logratio = new_lp - old_lp
+// Update diagnostics (the *_diag entry points: the DIAG instances of the kernels below).  Per minibatch, from the very logratio = new_lp - old_lp
 // and r = exp(logratio) the loss is made of (CleanRL's ppo.py):
 //   approx_kl = mean((r - 1) - logratio)          clipfrac = mean(|r - 1| > clip)
 // and the block diag[PC_DIAG_FLOATS]: [0] sum of approx_kl over the steps evaluated, [1] sum of clipfrac, [2] steps evaluated,
@@ -126,16 +55,27 @@ __device__ __forceinline__ bool diag_book(float* __restrict__ diag, const DiagSu
     return !stop;
 }
 
-// K7d: K7 with the diagnostics (its own kernel: K7 above stays as it is).  The same loss and gradient operations in the same order.
-template <int AMAX>
-__global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __restrict__ logits, const float* __restrict__ values,
-                                                             const float* __restrict__ act, const float* __restrict__ old_lp,
-                                                             const float* __restrict__ adv, const float* __restrict__ ret, const int B,
-                                                             const int A, const float clip, const float vf, const float ec,
-                                                             float* __restrict__ dlogits, float* __restrict__ dvalues,
-                                                             float* __restrict__ metrics, float* __restrict__ diag, const float kl_stop) {
+// K7: clipped-PPO loss of one minibatch, forward AND backward w.r.t. the network outputs (train.py:235-255):
+//   ratio = exp(new_lp - old_lp); A = (adv - mean) / max(std_unbiased, 1e-5)
+//   L_pi = mean(max(-A r, -A clamp(r, 1-c, 1+c))); L_v = 0.5 mean((v - ret)^2); H = mean(entropy)
+//   loss = L_pi + vf L_v - ec H
+// One workgroup, one sample per thread (B <= 1024).  Gradients as autograd produces them:
+//   dloss/dv_i      = vf (v_i - ret_i) / B
+//   dloss/dlp_i     = (1/B) r_i * (-A_i if -A_i r_i >= -A_i clamp(r_i) else 0)     [torch.max / clamp backward]
+//   dloss/dlogit_ik = dloss/dlp_i (1[k = a_i] - p_ik) + (ec/B) p_ik (log p_ik + H_i)
+// metrics[0..3] += (L_pi, L_v, H, loss)  (train.py:263-266).
+// DIAG (pc_ppo_loss_diag): the stop flag is read first, the KL and clipped terms come from the very r and logratio of the loss, and
+// thread 0 books the step (diag_book); the plain instance ignores `diag` and `kl_stop`.  The same loss and gradient operations in the
+// same order either way.
+template <int AMAX, bool DIAG>
+__global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict__ logits, const float* __restrict__ values,
+                                                        const float* __restrict__ act, const float* __restrict__ old_lp,
+                                                        const float* __restrict__ adv, const float* __restrict__ ret, const int B,
+                                                        const int A, const float clip, const float vf, const float ec,
+                                                        float* __restrict__ dlogits, float* __restrict__ dvalues,
+                                                        float* __restrict__ metrics, float* __restrict__ diag, const float kl_stop) {
     __shared__ float sh[16];
-    if (diag[4] != 0.0f) return;   // (uniform) the epoch's update has stopped
+    if constexpr (DIAG) if (diag[4] != 0.0f) return;   // (uniform) the epoch's update has stopped
     const int i = threadIdx.x;
     const bool on = i < B;
     const float invB = 1.0f / (float)B;
@@ -144,7 +84,7 @@ __global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __rest
     const float dev = on ? a_raw - mean : 0.0f;
     const float var = block_sum(dev * dev, sh) / (float)(B - 1);   // unbiased, as Tensor.std() (train.py:239)
     const float sd = fmaxf(sqrtf(var), 1e-5f);                     // torch.max(std, 1e-5) (train.py:239-240)
-    float pl = 0.0f, vl = 0.0f, ent = 0.0f, kl = 0.0f, clipped = 0.0f;
+    float pl = 0.0f, vl = 0.0f, ent = 0.0f, kl = 0.0f, clipped = 0.0f;   // (kl, clipped: DIAG only)
     if (on) {
         float l[AMAX];
         float mx = -INFINITY;
@@ -168,8 +108,10 @@ __global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __rest
             if (k == a) new_lp = lpk[k];
         }
         const float r = expf(new_lp - old_lp[i]);                                  // :235
-        kl = (r - 1.0f) - (new_lp - old_lp[i]);
-        clipped = fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+        if constexpr (DIAG) {
+            kl = (r - 1.0f) - (new_lp - old_lp[i]);
+            clipped = fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+        }
         const float An = dev / sd;                                                 // :238-240
         const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
         const float pl1 = -An * r, pl2 = -An * rc;                                 // :243-244
@@ -183,8 +125,10 @@ __global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __rest
             if (k < A) dlogits[i * A + k] = g_lp * ((k == a ? 1.0f : 0.0f) - pk[k]) + ec * invB * pk[k] * (lpk[k] + ent);
     }
     const float s_pl = block_sum(pl, sh) * invB, s_vl = block_sum(vl, sh) * invB, s_en = block_sum(ent, sh) * invB;
-    const DiagSums d{block_sum(kl, sh) * invB, block_sum(clipped, sh) * invB};
-    if (i == 0 && !diag_book(diag, d, kl_stop)) return;   // a stopping step adds nothing to the metrics either
+    if constexpr (DIAG) {
+        const DiagSums d{block_sum(kl, sh) * invB, block_sum(clipped, sh) * invB};
+        if (i == 0 && !diag_book(diag, d, kl_stop)) return;   // a stopping step adds nothing to the metrics either
+    }
     if (i == 0) {
         metrics[0] += s_pl;
         metrics[1] += s_vl;
@@ -196,45 +140,16 @@ __global__ __launch_bounds__(1024) void ppo_loss_diag_kernel(const float* __rest
 // K8: nn.utils.clip_grad_norm_(params, max_norm) (train.py:260) + Adam.step() (train.py:261, lr from the device,
 // eps 1e-5, betas (0.9, 0.999), no weight decay / amsgrad) over the flat parameter bucket, one workgroup.
 // grad_scale folds the 1/world_size of the gradient average in.  state[0] = step count (float), updated here.
+// DIAG (pc_clip_adam_diag): returns at once when the update has stopped; the plain instance ignores `diag`.
+template <bool DIAG>
 __global__ __launch_bounds__(1024) void clip_adam_kernel(float* __restrict__ param, float* __restrict__ grad,
                                                          float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
                                                          float* __restrict__ step_count, const float* __restrict__ lr_dev,
                                                          const int n, const float max_norm, const float grad_scale,
-                                                         const float beta1, const float beta2, const float eps) {
+                                                         const float beta1, const float beta2, const float eps,
+                                                         const float* __restrict__ diag) {
     __shared__ float sh[16];
-    float ss = 0.0f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float g = grad[i] * grad_scale;
-        ss += g * g;
-    }
-    const float total_norm = sqrtf(block_sum(ss, sh));
-    const float coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);   // clip_coef_clamped
-    const float step = step_count[0] + 1.0f;
-    const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
-    const float step_size = lr_dev[0] / bc1;
-    const float bc2_sqrt = sqrtf(bc2);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float g = grad[i] * grad_scale * coef;
-        grad[i] = g;                                                   // clip_grad_norm_ scales the grads in place
-        const float m = exp_avg[i] + (1.0f - beta1) * (g - exp_avg[i]);            // exp_avg.lerp_(grad, 1 - beta1)
-        const float v = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;            // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-        exp_avg[i] = m;
-        exp_avg_sq[i] = v;
-        const float denom = sqrtf(v) / bc2_sqrt + eps;
-        param[i] -= step_size * (m / denom);                                        // param.addcdiv_(exp_avg, denom, -step_size)
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) step_count[0] = step;
-}
-// K8d: K8 that returns at once when the update has stopped (its own kernel: K8 above stays as it is)
-__global__ __launch_bounds__(1024) void clip_adam_diag_kernel(float* __restrict__ param, float* __restrict__ grad,
-                                                              float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                                              float* __restrict__ step_count, const float* __restrict__ lr_dev,
-                                                              const int n, const float max_norm, const float grad_scale,
-                                                              const float beta1, const float beta2, const float eps,
-                                                              const float* __restrict__ diag) {
-    __shared__ float sh[16];
-    if (diag[4] != 0.0f) return;   // (uniform) stopped: parameters, moments, gradient and step counter stay
+    if constexpr (DIAG) if (diag[4] != 0.0f) return;   // (uniform) stopped: parameters, moments, gradient and step counter stay
     float ss = 0.0f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float g = grad[i] * grad_scale;

@@ -61,6 +61,7 @@
 #include <new>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <climits>
@@ -135,6 +136,22 @@ bool valid_device(int device) {
 
 // a reward scale whose inverse decodes the episode statistics' rewards: finite, positive, with a finite inverse
 bool valid_reward_scale(double s) { return std::isfinite(s) && s > 0.0 && std::isfinite(1.0 / s); }
+
+// the actor / critic pair every MLP kernel is written for, D -> 256 -> A and D -> 256 -> 1, and its flat parameter count (update.hpp, K10-K12)
+bool mlp_shape_ok(int D, int H, int A) { return H == 256 && A >= 1 && A <= 15 && D >= 1 && D <= 40; }
+int64_t mlp_n_param(int D, int H, int A) { return 2 * ((int64_t)H * D + H) + (int64_t)A * H + A + H + 1; }
+int64_t pad4(int64_t n) { return (n + 3) & ~(int64_t)3; }      // rows of parameters / partials start 16-byte aligned
+
+// The compiled shapes of K10 / K10L.  CarEnv's (Discrete(9); 6 + 12 / 17 / 33 rays) have their action count and observation width compiled in
+// -- and, in K10, the deferred clip + Adam prologue; every other shape takes the generic form of its width.  f(DMAX, AC, DC): integral_constants.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> void with_mlp_shape(int D, int A, F&& f) {
+    if (A == 9 && D == 23) f(IntC<24>{}, IntC<9>{}, IntC<23>{});
+    else if (A == 9 && D == 18) f(IntC<24>{}, IntC<9>{}, IntC<18>{});
+    else if (A == 9 && D == 39) f(IntC<40>{}, IntC<9>{}, IntC<39>{});
+    else if (D <= 24) f(IntC<24>{}, IntC<0>{}, IntC<0>{});
+    else f(IntC<40>{}, IntC<0>{}, IntC<0>{});
+}
 
 // Launch a 512-thread kernel with `lds` bytes of dynamic LDS.  Its limit is raised to 160 KB once per (kernel, device), not on every
 // call (pc_env_step is on the per-step path); device ids from 64 on have no bit in the set and raise it on every call.
@@ -1316,7 +1333,7 @@ extern "C" {
 int pc_policy_create(int device, int D, int H, int A, int precision, int split, pc_policy** out) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!out || precision < -1 || precision > 2 || split < -1 || split > 1) return PC_ERR_INVALID_ARG;
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
+    if (!mlp_shape_ok(D, H, A)) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
     pc_policy* p = new (std::nothrow) pc_policy;
     if (!p) return PC_ERR_INVALID_ARG;
     p->device = device;
@@ -1386,7 +1403,7 @@ static int64_t policy_image_floats_impl(int prec, int D) { return prec ? polx_im
 static int policy_pack_impl(int device, int prec, int D, int H, int A, const float* aW1, const float* ab1, const float* aW2, const float* ab2,
                             const float* cW1, const float* cb1, const float* cW2, const float* cb2, float* image, int* status, void* stream) {
     if (!aW1 || !ab1 || !aW2 || !ab2 || !cW1 || !cb1 || !cW2 || !cb2 || !image) return PC_ERR_INVALID_ARG;
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;
+    if (!mlp_shape_ok(D, H, A)) return PC_ERR_UNSUPPORTED;
     if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
@@ -1409,7 +1426,7 @@ static int policy_act_impl(int device, int prec, int split_mode, const float* ob
                            uint64_t offset, const uint64_t* offset_dev, int64_t* action, float* action_f32, float* logprob, float* value,
                            float* logits_out, void* stream) {
     if (!obs || !image || !action || !logprob || !value || N < 1) return PC_ERR_INVALID_ARG;
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
+    if (!mlp_shape_ok(D, H, A)) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
     if (!valid_device(device)) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
@@ -1467,6 +1484,9 @@ int pc_ppo_gather(int device, const int64_t* idx, int B, int D, const float* obs
     return PC_OK;
 }
 
+// 1.5 x target_kl as the kernels' float threshold (SB3's rule); target_kl <= 0 or NaN: 0 = never stop
+static float kl_stop_of(double target_kl) { return target_kl > 0.0 ? (float)(1.5 * target_kl) : 0.0f; }
+
 int pc_ppo_loss(int device, const float* logits, const float* values, const float* act, const float* old_logprob,
                 const float* adv, const float* ret, int B, int A, double clip_ratio, double vf_coef, double ent_coef,
                 float* dlogits, float* dvalues, float* metrics, void* stream) {
@@ -1476,8 +1496,8 @@ int pc_ppo_loss(int device, const float* logits, const float* values, const floa
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int threads = ((B + 63) / 64) * 64;
-    hipLaunchKernelGGL(ppo_loss_kernel<16>, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, values, act, old_logprob, adv,
-                       ret, B, A, (float)clip_ratio, (float)vf_coef, (float)ent_coef, dlogits, dvalues, metrics);
+    hipLaunchKernelGGL((ppo_loss_kernel<16, false>), dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, values, act, old_logprob, adv,
+                       ret, B, A, (float)clip_ratio, (float)vf_coef, (float)ent_coef, dlogits, dvalues, metrics, nullptr, 0.0f);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
@@ -1488,14 +1508,11 @@ int pc_clip_adam(int device, float* param, float* grad, float* exp_avg, float* e
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr_dev || n < 1 || n > (1 << 26)) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
-                       lr_dev, (int)n, (float)max_norm, (float)grad_scale, (float)beta1, (float)beta2, (float)eps);
+    hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
+                       lr_dev, (int)n, (float)max_norm, (float)grad_scale, (float)beta1, (float)beta2, (float)eps, nullptr);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
-
-// 1.5 x target_kl as the kernels' float threshold (SB3's rule); target_kl <= 0 or NaN: 0 = never stop
-static float kl_stop_of(double target_kl) { return target_kl > 0.0 ? (float)(1.5 * target_kl) : 0.0f; }
 
 int pc_ppo_loss_diag(int device, const float* logits, const float* values, const float* act, const float* old_logprob,
                      const float* adv, const float* ret, int B, int A, double clip_ratio, double vf_coef, double ent_coef,
@@ -1507,7 +1524,7 @@ int pc_ppo_loss_diag(int device, const float* logits, const float* values, const
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int threads = ((B + 63) / 64) * 64;
-    hipLaunchKernelGGL(ppo_loss_diag_kernel<16>, dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, values, act, old_logprob, adv,
+    hipLaunchKernelGGL((ppo_loss_kernel<16, true>), dim3(1), dim3(threads), 0, (hipStream_t)stream, logits, values, act, old_logprob, adv,
                        ret, B, A, (float)clip_ratio, (float)vf_coef, (float)ent_coef, dlogits, dvalues, metrics, diag, kl_stop_of(target_kl));
     HIPCHK(hipGetLastError());
     return PC_OK;
@@ -1521,7 +1538,7 @@ int pc_clip_adam_diag(int device, float* param, float* grad, float* exp_avg, flo
     if (device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(clip_adam_diag_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
+    hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
                        lr_dev, (int)n, (float)max_norm, (float)grad_scale, (float)beta1, (float)beta2, (float)eps, diag);
     HIPCHK(hipGetLastError());
     return PC_OK;
@@ -1834,111 +1851,124 @@ static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_
     return PC_OK;
 }
 
-int64_t pc_ppo_workspace_floats(int B, int D, int H, int A) {
-    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
-    const int64_t n_param = 2 * ((int64_t)H * D + H) + (int64_t)A * H + A + H + 1;
-    const int64_t n_part = (B + FB_S - 1) / FB_S;
-    return n_part * ((n_param + 3) & ~(int64_t)3) + n_part * 4 + (n_param + 255) / 256;
+// ---- the PPO minibatch step (kernels/update.hpp, update_large.hpp): one shape menu (with_mlp_shape), one workspace layout, one launch sequence
+static bool mb_defer_shape(int D, int A) {      // the menu's entries with the shape compiled in
+    bool compiled = false;
+    with_mlp_shape(D, A, [&](auto, auto ac, auto) { compiled = decltype(ac)::value > 0; });
+    return compiled;
 }
+static bool small_batch(int B) { return B >= 2 && B <= 1024; }      // K10: one workgroup per 8 samples, statistics by one workgroup
+static bool large_shape(int B, int D, int H, int A) { return mlp_shape_ok(D, H, A) && B > 1024 && B <= PC_PPO_LARGE_MAX_B; }
 
-// the diagnostics forms append a second per-workgroup partial (sum of KL terms, clipped samples) to that layout
-int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
-    const int64_t base = pc_ppo_workspace_floats(B, D, H, A);
-    return base < 0 ? base : base + 2 * (int64_t)((B + FB_S - 1) / FB_S);
-}
-
-// the layout of pc_ppo_minibatch's workspace and the launches of one minibatch step
+// The workspace of one minibatch step -- the ONLY place that knows its layout: n_part gradient partials (K10: one per group of 8
+// samples; parts > 0: K10L's fixed grid, pc_ppo_large_parts), their (pl, vl, ent, -) partials, K11's squared-norm partials and, for
+// the diagnostics forms alone, a second per-workgroup partial (sum of KL terms, clipped samples).
 struct MbPlan {
     int n_param, n_part, n_blk, n_pad, HD, mid_end;
     float *partial, *metric_partial, *norm_partial, *diag_partial;
-    MbPlan(int B, int D, int H, int A, float* workspace, int parts = 0) {      // parts > 0: K10L's fixed grid (pc_ppo_large_parts)
-        n_param = 2 * (H * D + H) + A * H + A + H + 1;
+    MbPlan(int B, int D, int H, int A, float* workspace, int parts = 0) {
+        n_param = (int)mlp_n_param(D, H, A);
         n_part = parts > 0 ? parts : (B + FB_S - 1) / FB_S;
         n_blk = (n_param + 255) / 256;
-        n_pad = (n_param + 3) & ~3;          // a partial's row stride: 16-byte aligned rows
+        n_pad = (int)pad4(n_param);          // a partial's row stride
         HD = H * D;
         mid_end = HD + H + A * H + A;        // natural offset of critic.0.weight (ppo_fwdbwd_body's o_cW1)
         partial = workspace;
         metric_partial = partial + (size_t)n_part * n_pad;
         norm_partial = metric_partial + n_part * 4;
-        diag_partial = norm_partial + n_blk;     // (pc_ppo_diag_workspace_floats: only the diagnostics forms touch it)
+        diag_partial = norm_partial + n_blk;
     }
+    int64_t floats(bool diag) const { return (int64_t)n_part * n_pad + n_part * 4 + n_blk + (diag ? 2 * n_part : 0); }
 };
 
-static void launch_fwdbwd(const MbPlan& pl, const int64_t* idx, const float* prep, int B, int D, int A, const float* obs, const float* act,
-                          const float* old_logprob, const float* adv, const float* ret, const float* param, double clip_ratio, double vf_coef,
-                          double ent_coef, const AdamDefer& df, hipStream_t st) {
-#define PC_FB(DM, ACV, DCV, DF)                                                                                          \
-    hipLaunchKernelGGL((ppo_fwdbwd_kernel<DM, ACV, DCV, DF>), dim3(pl.n_part), dim3(256), 0, st, idx, B, D, A, obs, act, old_logprob, adv, ret, param, \
-                       (float)clip_ratio, (float)vf_coef, (float)ent_coef, pl.partial, pl.metric_partial, prep, df)
-    // CarEnv's shapes (Discrete(9); 6 + 12 / 17 / 33 rays) have their action count and observation width compiled in -- and the
-    // deferred clip + Adam prologue (mb_defer_shape)
-    if (A == 9 && D == 23) { if (df.grad) PC_FB(24, 9, 23, true); else PC_FB(24, 9, 23, false); }
-    else if (A == 9 && D == 18) { if (df.grad) PC_FB(24, 9, 18, true); else PC_FB(24, 9, 18, false); }
-    else if (A == 9 && D == 39) { if (df.grad) PC_FB(40, 9, 39, true); else PC_FB(40, 9, 39, false); }
-    else if (D <= 24) PC_FB(24, 0, 0, false);
-    else PC_FB(40, 0, 0, false);
-#undef PC_FB
-}
-static void launch_fwdbwd_diag(const MbPlan& pl, const int64_t* idx, const float* prep, int B, int D, int A, const float* obs, const float* act,
-                               const float* old_logprob, const float* adv, const float* ret, const float* param, double clip_ratio, double vf_coef,
-                               double ent_coef, const float* diag, hipStream_t st) {
-#define PC_FB(DM, ACV, DCV)                                                                                              \
-    hipLaunchKernelGGL((ppo_fwdbwd_diag_kernel<DM, ACV, DCV>), dim3(pl.n_part), dim3(256), 0, st, idx, B, D, A, obs, act, old_logprob, adv, ret, param, \
-                       (float)clip_ratio, (float)vf_coef, (float)ent_coef, pl.partial, pl.metric_partial, prep, diag, pl.diag_partial)
-    if (A == 9 && D == 23) PC_FB(24, 9, 23);       // (launch_fwdbwd's menu)
-    else if (A == 9 && D == 18) PC_FB(24, 9, 18);
-    else if (A == 9 && D == 39) PC_FB(40, 9, 39);
-    else if (D <= 24) PC_FB(24, 0, 0);
-    else PC_FB(40, 0, 0);
-#undef PC_FB
-}
-static bool mb_defer_shape(int D, int A) { return A == 9 && (D == 18 || D == 23 || D == 39); }
-
-static void launch_reduce(const MbPlan& pl, int B, double vf_coef, double ent_coef, float* grad, float* metrics, float* step_count, hipStream_t st) {
-    hipLaunchKernelGGL(grad_reduce_kernel, dim3(pl.n_blk), dim3(256), 0, st, pl.partial, pl.n_part, pl.n_param, pl.HD, pl.mid_end, pl.n_pad, grad,
-                       pl.norm_partial, pl.metric_partial, B, (float)vf_coef, (float)ent_coef, metrics, step_count);
+int64_t pc_ppo_workspace_floats(int B, int D, int H, int A) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!mlp_shape_ok(D, H, A) || !small_batch(B)) return PC_ERR_UNSUPPORTED;
+    return MbPlan(B, D, H, A, nullptr).floats(false);
 }
 
-static void launch_adam(const MbPlan& pl, const float* p_in, const float* m_in, const float* v_in, float* grad, float* p_out, float* m_out,
-                        float* v_out, const float* step_count, const float* lr_dev, double max_norm, double beta1, double beta2, double eps,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(adam_kernel, dim3(pl.n_blk), dim3(256), 0, st, p_in, m_in, v_in, grad, p_out, m_out, v_out, step_count, lr_dev,
-                       pl.norm_partial, pl.n_blk, pl.n_param, (float)max_norm, (float)beta1, (float)beta2, (float)eps);
+int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!mlp_shape_ok(D, H, A) || !small_batch(B)) return PC_ERR_UNSUPPORTED;
+    return MbPlan(B, D, H, A, nullptr).floats(true);
 }
 
-static int ppo_minibatch_impl(int device, const int64_t* idx, const float* prep, int B, int D, int H, int A, const float* obs,
-                              const float* act, const float* old_logprob, const float* adv, const float* ret, float* param, float* grad,
-                              float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double clip_ratio,
-                              double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics,
-                              float* workspace, int apply, void* stream, float* diag = nullptr, double target_kl = 0.0) {
-    if (!param || !grad || !metrics || !workspace) return PC_ERR_INVALID_ARG;
-    if (!prep && (!idx || !obs || !act || !old_logprob || !adv || !ret)) return PC_ERR_INVALID_ARG;
-    if (apply == 1 && (!exp_avg || !exp_avg_sq || !step_count || !lr_dev)) return PC_ERR_INVALID_ARG;
-    if (apply == 2 && !step_count) return PC_ERR_INVALID_ARG;
-    if (apply < 0 || apply > 2) return PC_ERR_INVALID_ARG;
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
-    if (diag && apply == 2) return PC_ERR_UNSUPPORTED;      // (the ranks of a multi-rank step would have to agree on the stop)
-    if (diag && device < 0) return PC_ERR_NO_DEVICE;
+// One minibatch step as the entry points hand it over
+struct MbSamples {      // the rollout's tensors and this minibatch's indices, or (prep) a block ppo_prepare_kernel gathered
+    const int64_t* idx; const float *obs, *act, *old_logprob, *adv, *ret, *prep;
+    bool complete() const { return prep || (idx && obs && act && old_logprob && adv && ret); }
+};
+struct MbState { float *param, *grad, *exp_avg, *exp_avg_sq, *step_count; const float* lr_dev; };
+struct MbCoef { double clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps; };
+struct MbStep {
+    MbSamples in; MbState s; MbCoef c;
+    float *metrics, *workspace;
+    int apply;                  // 0: gradient only; 1: + clip + Adam; 2: + the step counter (the caller exchanges, then pc_clip_adam_advanced)
+    float* diag = nullptr; double target_kl = 0.0;      // the diagnostics forms
+};
+// the minibatch entry points share their parameter names: their step, IN the samples, then (diag, target_kl) for the diagnostics forms
+#define PC_MB_STEP(IN, ...)                                                                                                              \
+    MbStep{IN, {param, grad, exp_avg, exp_avg_sq, step_count, lr_dev}, {clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps}, \
+           metrics, workspace, apply, ##__VA_ARGS__}
+static int check_apply_args(const MbStep& m) {
+    if (!m.s.param || !m.s.grad || !m.metrics || !m.workspace) return PC_ERR_INVALID_ARG;
+    if (m.apply == 1 && (!m.s.exp_avg || !m.s.exp_avg_sq || !m.s.step_count || !m.s.lr_dev)) return PC_ERR_INVALID_ARG;
+    if (m.apply == 2 && !m.s.step_count) return PC_ERR_INVALID_ARG;
+    return m.apply < 0 || m.apply > 2 ? PC_ERR_INVALID_ARG : PC_OK;
+}
+
+// K10 (its diagnostics form with `diag`, its deferred form with df.grad) on `param`
+static void launch_fwdbwd(const MbPlan& pl, int B, int D, int A, const MbSamples& in, const float* param, const MbCoef& c, const AdamDefer& df,
+                          const float* diag, hipStream_t st) {
+    with_mlp_shape(D, A, [&](auto dm, auto ac, auto dc) {
+        constexpr int DM = decltype(dm)::value, AC = decltype(ac)::value, DC = decltype(dc)::value;
+        auto go = [&](auto kernel, auto... extra) {
+            hipLaunchKernelGGL(kernel, dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.old_logprob, in.adv, in.ret, param,
+                               (float)c.clip_ratio, (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial, in.prep, extra...);
+        };
+        if (diag) return go(ppo_fwdbwd_diag_kernel<DM, AC, DC>, diag, pl.diag_partial);
+        if constexpr (AC > 0) if (df.grad) return go(ppo_fwdbwd_kernel<DM, AC, DC, true>, df);
+        go(ppo_fwdbwd_kernel<DM, AC, DC, false>, df);
+    });
+}
+// K11 (its diagnostics form with `diag`)
+static void launch_reduce(const MbPlan& pl, int B, const MbCoef& c, float* grad, float* metrics, float* step_count, hipStream_t st,
+                          float* diag = nullptr, double target_kl = 0.0) {
+    auto go = [&](auto kernel, auto... extra) {
+        hipLaunchKernelGGL(kernel, dim3(pl.n_blk), dim3(256), 0, st, pl.partial, pl.n_part, pl.n_param, pl.HD, pl.mid_end, pl.n_pad, grad,
+                           pl.norm_partial, pl.metric_partial, B, (float)c.vf_coef, (float)c.ent_coef, metrics, step_count, extra...);
+    };
+    if (diag) go(grad_reduce_diag_kernel, diag, (const float*)pl.diag_partial, kl_stop_of(target_kl));
+    else go(grad_reduce_kernel);
+}
+// K12 (its diagnostics form with `diag`): state `in` -> state `out`
+static void launch_adam(const MbPlan& pl, const float* p_in, const float* m_in, const float* v_in, const MbState& out, const MbCoef& c, hipStream_t st,
+                        const float* diag = nullptr) {
+    auto go = [&](auto kernel, auto... extra) {
+        hipLaunchKernelGGL(kernel, dim3(pl.n_blk), dim3(256), 0, st, p_in, m_in, v_in, out.grad, out.param, out.exp_avg, out.exp_avg_sq,
+                           (const float*)out.step_count, out.lr_dev, (const float*)pl.norm_partial, pl.n_blk, pl.n_param, (float)c.max_norm,
+                           (float)c.beta1, (float)c.beta2, (float)c.eps, extra...);
+    };
+    if (diag) go(adam_diag_kernel, diag);
+    else go(adam_kernel);
+}
+// what follows K10 / K10L in every step: the reduction, and with apply == 1 clip + Adam in place
+static void launch_reduce_apply(const MbPlan& pl, int B, const MbStep& m, hipStream_t st) {
+    launch_reduce(pl, B, m.c, m.s.grad, m.metrics, m.apply ? m.s.step_count : nullptr, st, m.diag, m.target_kl);
+    if (m.apply == 1) launch_adam(pl, m.s.param, m.s.exp_avg, m.s.exp_avg_sq, m.s, m.c, st, m.diag);
+}
+
+static int ppo_minibatch_impl(int device, int B, int D, int H, int A, const MbStep& m, void* stream) {
+    if (const int rc = check_apply_args(m); rc != PC_OK || !m.in.complete()) return PC_ERR_INVALID_ARG;
+    if (!mlp_shape_ok(D, H, A) || !small_batch(B)) return PC_ERR_UNSUPPORTED;
+    if (m.diag && m.apply == 2) return PC_ERR_UNSUPPORTED;      // (the ranks of a multi-rank step would have to agree on the stop)
+    if (m.diag && device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    const MbPlan pl(B, D, H, A, workspace);
+    const MbPlan pl(B, D, H, A, m.workspace);
     hipStream_t st = (hipStream_t)stream;
-    if (diag) {     // the diagnostics forms of the same three launches (update.hpp: DIAG)
-        launch_fwdbwd_diag(pl, idx, prep, B, D, A, obs, act, old_logprob, adv, ret, param, clip_ratio, vf_coef, ent_coef, diag, st);
-        hipLaunchKernelGGL(grad_reduce_diag_kernel, dim3(pl.n_blk), dim3(256), 0, st, pl.partial, pl.n_part, pl.n_param, pl.HD, pl.mid_end, pl.n_pad,
-                           grad, pl.norm_partial, pl.metric_partial, B, (float)vf_coef, (float)ent_coef, metrics, apply ? step_count : nullptr, diag,
-                           pl.diag_partial, kl_stop_of(target_kl));
-        if (apply == 1)
-            hipLaunchKernelGGL(adam_diag_kernel, dim3(pl.n_blk), dim3(256), 0, st, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count,
-                               lr_dev, pl.norm_partial, pl.n_blk, pl.n_param, (float)max_norm, (float)beta1, (float)beta2, (float)eps, diag);
-        HIPCHK(hipGetLastError());
-        return PC_OK;
-    }
-    launch_fwdbwd(pl, idx, prep, B, D, A, obs, act, old_logprob, adv, ret, param, clip_ratio, vf_coef, ent_coef, AdamDefer{}, st);
-    launch_reduce(pl, B, vf_coef, ent_coef, grad, metrics, apply ? step_count : nullptr, st);
-    if (apply == 1) launch_adam(pl, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
+    launch_fwdbwd(pl, B, D, A, m.in, m.s.param, m.c, AdamDefer{}, m.diag, st);
+    launch_reduce_apply(pl, B, m, st);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
@@ -1949,9 +1979,7 @@ int pc_ppo_minibatch(int device, const int64_t* idx, int B, int D, int H, int A,
                      double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
                      void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
-    return ppo_minibatch_impl(device, idx, nullptr, B, D, H, A, obs, act, old_logprob, adv, ret, param, grad, exp_avg, exp_avg_sq,
-                              step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics, workspace, apply,
-                              stream);
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, act, old_logprob, adv, ret, nullptr})), stream);
 }
 
 int pc_ppo_minibatch_diag(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
@@ -1961,14 +1989,12 @@ int pc_ppo_minibatch_diag(int device, const int64_t* idx, int B, int D, int H, i
                           float* diag, double target_kl, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!diag) return PC_ERR_INVALID_ARG;
-    return ppo_minibatch_impl(device, idx, nullptr, B, D, H, A, obs, act, old_logprob, adv, ret, param, grad, exp_avg, exp_avg_sq,
-                              step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics, workspace, apply,
-                              stream, diag, target_kl);
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, act, old_logprob, adv, ret, nullptr}), diag, target_kl), stream);
 }
 
 int64_t pc_ppo_prepared_floats(int B, int D) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
-    if (D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
+    if (D < 1 || D > 40 || !small_batch(B)) return PC_ERR_UNSUPPORTED;
     return (int64_t)B * (D + 4) + 4;
 }
 
@@ -1976,7 +2002,7 @@ int pc_ppo_prepare(int device, const int64_t* idx, int64_t idx_ld, int n_mb, int
                    const float* old_logprob, const float* adv, const float* ret, float* prepared, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!idx || !obs || !act || !old_logprob || !adv || !ret || !prepared || n_mb < 1 || idx_ld < B) return PC_ERR_INVALID_ARG;
-    if (D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
+    if (D < 1 || D > 40 || !small_batch(B)) return PC_ERR_UNSUPPORTED;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     hipLaunchKernelGGL(ppo_prepare_kernel, dim3(n_mb), dim3(256), 0, (hipStream_t)stream, idx, idx_ld, B, D, obs, act, old_logprob, adv, ret,
@@ -1991,9 +2017,7 @@ int pc_ppo_minibatch_prepared(int device, const float* prepared_mb, int B, int D
                               float* workspace, int apply, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!prepared_mb) return PC_ERR_INVALID_ARG;
-    return ppo_minibatch_impl(device, nullptr, prepared_mb, B, D, H, A, nullptr, nullptr, nullptr, nullptr, nullptr, param, grad, exp_avg,
-                              exp_avg_sq, step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics,
-                              workspace, apply, stream);
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{.prep = prepared_mb})), stream);
 }
 
 int pc_ppo_minibatch_prepared_diag(int device, const float* prepared_mb, int B, int D, int H, int A, float* param, float* grad, float* exp_avg,
@@ -2002,17 +2026,11 @@ int pc_ppo_minibatch_prepared_diag(int device, const float* prepared_mb, int B, 
                                    float* workspace, int apply, float* diag, double target_kl, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!prepared_mb || !diag) return PC_ERR_INVALID_ARG;
-    return ppo_minibatch_impl(device, nullptr, prepared_mb, B, D, H, A, nullptr, nullptr, nullptr, nullptr, nullptr, param, grad, exp_avg,
-                              exp_avg_sq, step_count, lr_dev, clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps, metrics,
-                              workspace, apply, stream, diag, target_kl);
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{.prep = prepared_mb}), diag, target_kl), stream);
 }
 
-// ---- the large-minibatch step (kernels/update_large.hpp): 1024 < B <= PC_PPO_LARGE_MAX_B
-static bool large_shape(int B, int D, int H, int A) {
-    return H == 256 && A >= 1 && A <= 15 && D >= 1 && D <= 40 && B > 1024 && B <= PC_PPO_LARGE_MAX_B;
-}
-// K10L's grid = its number of partials: one workgroup per group of 8 samples up to one per compute unit.  The ONE expression the
-// workspace size, the launch and pc_ppo_large_parts share.
+// ---- the large-minibatch step (kernels/update_large.hpp): 1024 < B <= PC_PPO_LARGE_MAX_B.  K10L's grid = its number of partials: one
+// workgroup per group of 8 samples up to one per compute unit.  The ONE expression the workspace size, the launch and pc_ppo_large_parts share.
 static int large_parts(int device, int B, int* out) {
     if (device < 0) return PC_ERR_NO_DEVICE;
     int cus = 0;
@@ -2034,9 +2052,7 @@ int64_t pc_ppo_large_workspace_floats(int device, int B, int D, int H, int A) {
     if (!large_shape(B, D, H, A)) return PC_ERR_UNSUPPORTED;
     int parts = 0;
     const int rc = large_parts(device, B, &parts);
-    if (rc != PC_OK) return rc;
-    const int64_t n_param = 2 * ((int64_t)H * D + H) + (int64_t)A * H + A + H + 1;
-    return parts * ((n_param + 3) & ~(int64_t)3) + parts * 4 + (n_param + 255) / 256;      // (MbPlan's layout with n_part = parts)
+    return rc != PC_OK ? rc : MbPlan(B, D, H, A, nullptr, parts).floats(false);
 }
 
 int64_t pc_ppo_adv_stats_workspace_doubles(int n_mb, int B) {
@@ -2067,39 +2083,31 @@ int pc_ppo_minibatch_large(int device, const int64_t* idx, int B, int D, int H, 
                            double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace,
                            int apply, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
-    if (!param || !grad || !metrics || !workspace) return PC_ERR_INVALID_ARG;
-    if (!idx || !obs || !act || !old_logprob || !adv || !ret || !adv_stats) return PC_ERR_INVALID_ARG;
-    if (apply == 1 && (!exp_avg || !exp_avg_sq || !step_count || !lr_dev)) return PC_ERR_INVALID_ARG;
-    if (apply == 2 && !step_count) return PC_ERR_INVALID_ARG;
-    if (apply < 0 || apply > 2) return PC_ERR_INVALID_ARG;
+    const MbStep m = PC_MB_STEP((MbSamples{idx, obs, act, old_logprob, adv, ret, nullptr}));
+    if (check_apply_args(m) != PC_OK || !m.in.complete() || !adv_stats) return PC_ERR_INVALID_ARG;
     if (!large_shape(B, D, H, A)) return PC_ERR_UNSUPPORTED;
     int parts = 0;
-    const int rc = large_parts(device, B, &parts);
-    if (rc != PC_OK) return rc;
+    if (const int rc = large_parts(device, B, &parts); rc != PC_OK) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const MbPlan pl(B, D, H, A, workspace, parts);
     hipStream_t st = (hipStream_t)stream;
-#define PC_FBL(DM, ACV, DCV)                                                                                                                   \
-    hipLaunchKernelGGL((ppo_fwdbwd_large_kernel<DM, ACV, DCV>), dim3(pl.n_part), dim3(256), 0, st, idx, B, D, A, obs, act, old_logprob, adv, ret, \
-                       adv_stats, param, (float)clip_ratio, (float)vf_coef, (float)ent_coef, pl.partial, pl.metric_partial)
-    if (A == 9 && D == 23) PC_FBL(24, 9, 23);       // (launch_fwdbwd's menu)
-    else if (A == 9 && D == 18) PC_FBL(24, 9, 18);
-    else if (A == 9 && D == 39) PC_FBL(40, 9, 39);
-    else if (D <= 24) PC_FBL(24, 0, 0);
-    else PC_FBL(40, 0, 0);
-#undef PC_FBL
-    launch_reduce(pl, B, vf_coef, ent_coef, grad, metrics, apply ? step_count : nullptr, st);
-    if (apply == 1) launch_adam(pl, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
+    with_mlp_shape(D, A, [&](auto dm, auto ac, auto dc) {
+        hipLaunchKernelGGL((ppo_fwdbwd_large_kernel<decltype(dm)::value, decltype(ac)::value, decltype(dc)::value>), dim3(pl.n_part), dim3(256), 0, st,
+                           idx, B, D, A, obs, act, old_logprob, adv, ret, adv_stats, (const float*)param, (float)clip_ratio, (float)vf_coef,
+                           (float)ent_coef, pl.partial, pl.metric_partial);
+    });
+    launch_reduce_apply(pl, B, m, st);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
 
+#undef PC_MB_STEP
+
 int64_t pc_ppo_epoch_state_floats(int D, int H, int A) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40) return PC_ERR_UNSUPPORTED;
-    const int64_t n_param = 2 * ((int64_t)H * D + H) + (int64_t)A * H + A + H + 1;
-    return 3 * ((n_param + 3) & ~(int64_t)3);
+    if (!mlp_shape_ok(D, H, A)) return PC_ERR_UNSUPPORTED;
+    return 3 * pad4(mlp_n_param(D, H, A));
 }
 
 int pc_ppo_epoch_prepared(int device, const float* prepared, int n_mb, int B, int D, int H, int A, float* param, float* grad, float* exp_avg,
@@ -2109,12 +2117,14 @@ int pc_ppo_epoch_prepared(int device, const float* prepared, int n_mb, int B, in
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!prepared || !param || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr_dev || !metrics || !workspace || !state2 || n_mb < 1)
         return PC_ERR_INVALID_ARG;
-    if (H != 256 || A < 1 || A > 15 || D < 1 || D > 40 || B < 2 || B > 1024) return PC_ERR_UNSUPPORTED;
+    if (!mlp_shape_ok(D, H, A) || !small_batch(B)) return PC_ERR_UNSUPPORTED;
     if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)state2) & 15) != 0) return PC_ERR_INVALID_ARG;   // 16-byte loads / stores
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const MbPlan pl(B, D, H, A, workspace);
     hipStream_t st = (hipStream_t)stream;
+    const MbState home{param, grad, exp_avg, exp_avg_sq, step_count, lr_dev};
+    const MbCoef c{clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps};
     // two generations of (param, exp_avg, exp_avg_sq): the caller's tensors and `state2`
     float* P[2] = {param, state2};
     float* M[2] = {exp_avg, state2 + pl.n_pad};
@@ -2124,30 +2134,16 @@ int pc_ppo_epoch_prepared(int device, const float* prepared, int n_mb, int B, in
     const bool defer = mb_defer_shape(D, A);     // (other shapes: the generic kernels, three launches per minibatch -- the same bits)
     for (int m = 0; m < n_mb; ++m) {
         AdamDefer df{};
-        if (!defer && m > 0) launch_adam(pl, param, exp_avg, exp_avg_sq, grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
-        if (defer && m > 0) {     // the previous minibatch's gradient is applied by this launch as it loads the parameters
-            df.grad = grad;
-            df.m_in = M[cur];
-            df.v_in = V[cur];
-            df.p_out = P[cur ^ 1];
-            df.m_out = M[cur ^ 1];
-            df.v_out = V[cur ^ 1];
-            df.norm_partial = pl.norm_partial;
-            df.n_norm = pl.n_blk;
-            df.step_count = step_count;
-            df.lr_dev = lr_dev;
-            df.max_norm = (float)max_norm;
-            df.beta1 = (float)beta1;
-            df.beta2 = (float)beta2;
-            df.eps = (float)eps;
-        }
-        launch_fwdbwd(pl, nullptr, prepared + (size_t)m * pf, B, D, A, nullptr, nullptr, nullptr, nullptr, nullptr, P[cur], clip_ratio, vf_coef, ent_coef,
-                      df, st);
+        if (!defer && m > 0) launch_adam(pl, param, exp_avg, exp_avg_sq, home, c, st);
+        if (defer && m > 0)      // the previous minibatch's gradient is applied by this launch as it loads the parameters
+            df = AdamDefer{grad, M[cur], V[cur], P[cur ^ 1], M[cur ^ 1], V[cur ^ 1], pl.norm_partial, pl.n_blk, step_count, lr_dev,
+                           (float)max_norm, (float)beta1, (float)beta2, (float)eps};
+        launch_fwdbwd(pl, B, D, A, {.prep = prepared + (size_t)m * pf}, P[cur], c, df, nullptr, st);
         if (defer && m > 0) cur ^= 1;
-        launch_reduce(pl, B, vf_coef, ent_coef, grad, metrics, step_count, st);
+        launch_reduce(pl, B, c, grad, metrics, step_count, st);
     }
     // the last gradient, and the state home to the caller's tensors
-    launch_adam(pl, P[cur], M[cur], V[cur], grad, param, exp_avg, exp_avg_sq, step_count, lr_dev, max_norm, beta1, beta2, eps, st);
+    launch_adam(pl, P[cur], M[cur], V[cur], home, c, st);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }

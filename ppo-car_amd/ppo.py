@@ -326,39 +326,46 @@ class PPOLearner:
                       file=sys.stderr, flush=True)
                 self.p2p = None
         self._capture_failed = False
-        self.graphs = bool(cfg.use_graphs) and self.device.type == "cuda"
-        self.fused = bool(cfg.fused_update) and self.device.type == "cuda" and 2 <= cfg.batch_size <= 1024
-        if self.fused:    # Adam state of the fused clip+Adam kernel (pc_clip_adam): flat, on the device
-            self.exp_avg = torch.zeros_like(self.flat_param)
-            self.exp_avg_sq = torch.zeros_like(self.flat_param)
-            self.step_count = torch.zeros(1, device=self.device)
-            self.lr_dev = torch.full((1,), cfg.learning_rate, device=self.device, dtype=torch.float32)
-        a1 = agent.actor[0] if isinstance(agent.actor, nn.Sequential) else None
-        self.custom = (self.fused and bool(cfg.custom_mlp) and agent._std_mlp() and a1.out_features == 256
-                       and lib.pc_ppo_workspace_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features) > 0)
+        cuda = self.device.type == "cuda"
+        self.graphs = bool(cfg.use_graphs) and cuda
+        self.n_minibatches = len(range(0, cfg.n_steps, cfg.batch_size))     # train.py:228
+        # ---- the update plan: which step runs, decided HERE and nowhere else.  Every condition is known now -- a minibatch is full when
+        # the rollout holds n_minibatches * batch_size samples -- so the path never changes between epochs.
+        #   "torch"  the reference's torch ops (any device)
+        #   "fused"  gather, loss fwd + bwd and clip + Adam as HIP kernels around torch's GEMMs (2 <= batch_size <= 1024)
+        #   "custom" the hand-written step, no library GEMM (pc_ppo_minibatch*: the standard 256-wide MLPs, batch_size <= 1024)
+        #   "large"  the large-minibatch kernels (PPOConfig.large_minibatch, batch_size > 1024: where "custom" ends)
+        B = cfg.batch_size
+        # the hand-written MLP kernels are asked for and the agent is theirs: the standard 256-wide pair, (D, H, A)
+        hand = cuda and bool(cfg.fused_update) and bool(cfg.custom_mlp) and agent._std_mlp() and agent.actor[0].out_features == 256
+        self._dha = (agent.actor[0].in_features, 256, agent.actor[2].out_features) if hand else None
+        if cuda and bool(cfg.fused_update) and 2 <= B <= 1024:
+            self.path = "custom" if hand and lib.pc_ppo_workspace_floats(B, *self._dha) > 0 else "fused"
+        elif hand and bool(cfg.large_minibatch) and B > 1024 and cfg.n_steps * cfg.n_envs >= self.n_minibatches * B:
+            self.path = "large"
+        else:
+            self.path = "torch"
+        self.fused, self.custom, self.large = self.path in ("fused", "custom"), self.path == "custom", self.path == "large"
+        self.flat_adam = self.path != "torch"      # the Adam state is exp_avg / exp_avg_sq / step_count / lr_dev, not a torch optimizer's
+        # ... and how the "custom" epoch runs: on minibatches gathered once per epoch (pc_ppo_prepare), as the deferred chain
+        # (pc_ppo_epoch_prepared); whether it is captured into one graph is update()'s question (_can_capture_update may change)
+        self.prepared = self.custom and bool(cfg.prepared_minibatches)
+        self.chained = self.prepared and bool(cfg.deferred_adam) and not self.collective
+        self._f = self._prep = self._state2 = None
+        if self.flat_adam:
+            self._alloc_flat_adam()
         if self.custom:
             ws_floats = lib.pc_ppo_diag_workspace_floats if self.diag_on else lib.pc_ppo_workspace_floats
-            self._ws = torch.empty(ws_floats(cfg.batch_size, a1.in_features, 256, agent.actor[2].out_features),
-                                   device=self.device, dtype=torch.float32)
-        self.n_minibatches = len(range(0, cfg.n_steps, cfg.batch_size))     # train.py:228
-        # the large-minibatch kernels (PPOConfig.large_minibatch): where the path above ends.  Every condition is known here -- a
-        # minibatch is full when the rollout holds n_minibatches * batch_size samples -- so the path never changes between epochs
-        self.large = (bool(cfg.large_minibatch) and cfg.batch_size > 1024 and bool(cfg.fused_update) and bool(cfg.custom_mlp)
-                      and self.device.type == "cuda" and agent._std_mlp() and a1.out_features == 256
-                      and cfg.n_steps * cfg.n_envs >= self.n_minibatches * cfg.batch_size)
+            self._ws = torch.empty(ws_floats(B, *self._dha), device=self.device, dtype=torch.float32)
+        if self.chained:      # the chain's second state generation (allocated here: never inside a capture)
+            self._state2 = torch.empty(lib.pc_ppo_epoch_state_floats(*self._dha), device=self.device)
         if self.large:
-            D, A, n_mb_total = a1.in_features, agent.actor[2].out_features, cfg.train_iters * self.n_minibatches
-            ws = lib.pc_ppo_large_workspace_floats(self._dev_index(), cfg.batch_size, D, 256, A)
+            n_mb_total = cfg.train_iters * self.n_minibatches
+            ws = lib.pc_ppo_large_workspace_floats(self._dev_index(), B, *self._dha)
             check(min(ws, 0), "pc_ppo_large_workspace_floats")        # (an unsupported shape is an error, not a reason to fall back)
-            self.exp_avg = torch.zeros_like(self.flat_param)
-            self.exp_avg_sq = torch.zeros_like(self.flat_param)
-            self.step_count = torch.zeros(1, device=self.device)
-            self.lr_dev = torch.full((1,), cfg.learning_rate, device=self.device, dtype=torch.float32)
             self._ws = torch.empty(ws, device=self.device, dtype=torch.float32)
             self._adv_stats = torch.empty(n_mb_total, 2, device=self.device, dtype=torch.float32)
-            self._adv_stats_ws = torch.empty(lib.pc_ppo_adv_stats_workspace_doubles(n_mb_total, cfg.batch_size), device=self.device,
-                                             dtype=torch.float64)
-        self.flat_adam = self.fused or self.large      # the Adam state is exp_avg / exp_avg_sq / step_count / lr_dev, not a torch optimizer's
+            self._adv_stats_ws = torch.empty(lib.pc_ppo_adv_stats_workspace_doubles(n_mb_total, B), device=self.device, dtype=torch.float64)
         self._epoch_graph = None
         if self.graphs:   # capturable Adam: step count and lr live on the device, so a captured step stays valid
             lr = torch.tensor(cfg.learning_rate, device=self.device, dtype=torch.float32)
@@ -370,13 +377,19 @@ class PPOLearner:
         idx = torch.empty(cfg.train_iters, self.n_minibatches * cfg.batch_size, dtype=torch.int64)
         # two pinned staging buffers, used alternately: epochs are queued without host synchronisation, so the async
         # H2D copy of epoch k may still be pending when the host draws the indices of epoch k+1
-        cuda = self.device.type == "cuda"
         self._idx_hosts = [idx.clone().pin_memory() if cuda else idx.clone() for _ in range(2)]
         self._idx_events = [torch.cuda.Event() if cuda else None for _ in range(2)]
         self._idx_turn = 0
         self._idx_dev = torch.empty_like(idx, device=self.device)
         self.metrics = torch.zeros(4, device=self.device)
         self._graph_key = None
+
+    def _alloc_flat_adam(self):
+        """The Adam state of the clip + Adam kernels: flat, on the device, the learning rate with it"""
+        self.exp_avg = torch.zeros_like(self.flat_param)
+        self.exp_avg_sq = torch.zeros_like(self.flat_param)
+        self.step_count = torch.zeros(1, device=self.device)
+        self.lr_dev = torch.full((1,), self.cfg.learning_rate, device=self.device, dtype=torch.float32)
 
     def current_lr(self):
         if self.flat_adam:
@@ -445,41 +458,47 @@ class PPOLearner:
             ev[1].record()
             self.exchange_events.append(ev)
 
-    def _custom_apply(self):
-        """clip + Adam after the gradient exchange of the custom (hand-written kernel) minibatch step: the step counter was
-        advanced by the gradient kernels (apply = 2), the bucket holds the sum over ranks."""
+    def _finish_step(self):
+        """After a gradient-only step (apply = 2: the step counter was advanced by the gradient kernels): the exchange, then clip +
+        Adam on the bucket, which holds the sum over ranks."""
         cfg = self.cfg
+        self._sum_gradients()
         check(lib.pc_clip_adam_advanced(self._dev_index(), self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
                                         self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(),
                                         self.flat_param.numel(), cfg.max_grad_norm, 1.0 / self.world_size, 0.9, 0.999, 1e-5,
                                         self._stream()), "pc_clip_adam_advanced")
 
+    def _step_tail(self):
+        """What every pc_ppo_minibatch* / pc_ppo_epoch_prepared call shares: state, coefficients, Adam's numbers, metrics, workspace"""
+        cfg = self.cfg
+        return (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.step_count.data_ptr(), self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
+                0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr())
+
+    def _minibatch_call(self, fn, fn_diag, first, *samples):
+        """One step through entry point `fn` (`fn_diag` with diagnostics; None: the path has no such form):
+        (device, first, B, D, H, A, *samples, tail, apply), apply = 1: clip + Adam inside the step; 2: the exchange step follows."""
+        args = (self._dev_index(), first, self.cfg.batch_size, *self._dha, *samples, *self._step_tail(), 2 if self.collective else 1)
+        if self.diag_on:
+            assert fn_diag is not None, "this update path has no diagnostics form (PPOConfig refuses the combination)"
+            check(fn_diag(*args, self.diag.data_ptr(), self.target_kl, self._stream()), fn_diag.__name__)
+        else:
+            check(fn(*args, self._stream()), fn.__name__)
+        if self.collective:
+            self._finish_step()
+
     def custom_minibatch_step(self, idx, obs, act, logprob, adv, ret):
         """pc_ppo_minibatch: gather + forward + loss + backward (+ clip + Adam when single-rank) with no library GEMM."""
-        cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
-        single = not self.collective
-        args = (self._dev_index(), idx.data_ptr(), cfg.batch_size, a1.in_features, a1.out_features, a2.out_features,
-                obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(), cfg.clip_ratio,
-                cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
-                self._ws.data_ptr(), 1 if single else 2)
-        if self.diag_on:
-            check(lib.pc_ppo_minibatch_diag(*args, self.diag.data_ptr(), self.target_kl, self._stream()), "pc_ppo_minibatch_diag")
-        else:
-            check(lib.pc_ppo_minibatch(*args, self._stream()), "pc_ppo_minibatch")
-        if not single:
-            self._sum_gradients()
-            self._custom_apply()
+        self._minibatch_call(lib.pc_ppo_minibatch, lib.pc_ppo_minibatch_diag, idx.data_ptr(), obs.data_ptr(), act.data_ptr(),
+                             logprob.data_ptr(), adv.data_ptr(), ret.data_ptr())
 
     def prepare_minibatches(self, idx_all, n_mb, obs, act, logprob, adv, ret):
         """pc_ppo_prepare: gather all train_iters x n_mb minibatches of the epoch in one launch (sample rows, per-sample
         scalars, advantage statistics), so that no minibatch step starts with dependent index -> row loads."""
-        cfg, a1 = self.cfg, self.agent.actor[0]
-        B, D = cfg.batch_size, a1.in_features
+        B, D = self.cfg.batch_size, self._dha[0]
         pf = lib.pc_ppo_prepared_floats(B, D)
         total = idx_all.shape[0] * n_mb
-        if getattr(self, "_prep", None) is None or self._prep.numel() != total * pf:
+        if self._prep is None or self._prep.numel() != total * pf:
             self._prep = torch.empty(total * pf, device=self.device)
         rows = idx_all if idx_all.is_contiguous() and idx_all.shape[1] == n_mb * B else None
         if rows is not None:                      # minibatch m = it * n_mb + mb starts at element m * B
@@ -496,33 +515,13 @@ class PPOLearner:
 
     def prepared_minibatch_step(self, m, pf):
         """pc_ppo_minibatch_prepared on block m of the prepared epoch (+ all-reduce and clip/Adam when multi-rank)."""
-        cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
-        single = not self.collective
-        args = (self._dev_index(), self._prep.data_ptr() + 4 * m * pf, cfg.batch_size, a1.in_features,
-                a1.out_features, a2.out_features, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
-                self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
-                0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr(), 1 if single else 2)
-        if self.diag_on:
-            check(lib.pc_ppo_minibatch_prepared_diag(*args, self.diag.data_ptr(), self.target_kl, self._stream()),
-                  "pc_ppo_minibatch_prepared_diag")
-        else:
-            check(lib.pc_ppo_minibatch_prepared(*args, self._stream()), "pc_ppo_minibatch_prepared")
-        if not single:
-            self._sum_gradients()
-            self._custom_apply()
+        self._minibatch_call(lib.pc_ppo_minibatch_prepared, lib.pc_ppo_minibatch_prepared_diag, self._prep.data_ptr() + 4 * m * pf)
 
     def _epoch_chain(self, n_mb_total):
         """pc_ppo_epoch_prepared: all minibatch steps of the epoch on the prepared blocks, two launches per minibatch (the clip +
         Adam step deferred into the next forward / backward launch) + one for the last gradient."""
-        cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
-        if getattr(self, "_state2", None) is None:
-            self._state2 = torch.empty(lib.pc_ppo_epoch_state_floats(a1.in_features, a1.out_features, a2.out_features), device=self.device)
-        check(lib.pc_ppo_epoch_prepared(self._dev_index(), self._prep.data_ptr(), n_mb_total, cfg.batch_size, a1.in_features, a1.out_features,
-                                        a2.out_features, self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                        self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(), cfg.clip_ratio,
-                                        cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
-                                        self._ws.data_ptr(), self._state2.data_ptr(), self._stream()), "pc_ppo_epoch_prepared")
+        check(lib.pc_ppo_epoch_prepared(self._dev_index(), self._prep.data_ptr(), n_mb_total, self.cfg.batch_size, *self._dha,
+                                        *self._step_tail(), self._state2.data_ptr(), self._stream()), "pc_ppo_epoch_prepared")
 
     def fused_minibatch_step(self, idx, obs, act, logprob, adv, ret):
         self._fused_fwd_bwd(idx, obs, act, logprob, adv, ret)
@@ -534,25 +533,15 @@ class PPOLearner:
         """The epoch's update with the large-minibatch kernels: the advantage statistics of all train_iters x n_mb minibatches in one
         launch pair, then pc_ppo_minibatch_large per minibatch on its slice of the epoch's index block (+ all-reduce and clip / Adam
         when there is an exchange step, as custom_minibatch_step)."""
-        cfg, a1, a2 = self.cfg, self.agent.actor[0], self.agent.actor[2]
         obs, act, logprob, adv, ret = args
-        B, total = cfg.batch_size, cfg.train_iters * n_mb
+        B, total = self.cfg.batch_size, self.cfg.train_iters * n_mb
         if not (idx_all.is_contiguous() and idx_all.shape[1] == n_mb * B):
             raise ValueError("large_minibatch: the epoch's index block must hold train_iters x n_minibatches full minibatches")
-        di, st, single = self._dev_index(), self._stream(), not self.collective
-        check(lib.pc_ppo_adv_stats(di, idx_all.data_ptr(), B, total, B, adv.data_ptr(), self._adv_stats.data_ptr(),
-                                   self._adv_stats_ws.data_ptr(), st), "pc_ppo_adv_stats")
+        check(lib.pc_ppo_adv_stats(self._dev_index(), idx_all.data_ptr(), B, total, B, adv.data_ptr(), self._adv_stats.data_ptr(),
+                                   self._adv_stats_ws.data_ptr(), self._stream()), "pc_ppo_adv_stats")
         for m in range(total):                    # minibatch m = it * n_mb + mb starts at element m * B
-            check(lib.pc_ppo_minibatch_large(di, idx_all.data_ptr() + 8 * m * B, B, a1.in_features, a1.out_features, a2.out_features,
-                                             obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                             self._adv_stats.data_ptr() + 8 * m, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
-                                             self.lr_dev.data_ptr(), cfg.clip_ratio, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, 0.9,
-                                             0.999, 1e-5, self.metrics.data_ptr(), self._ws.data_ptr(), 1 if single else 2, st),
-                  "pc_ppo_minibatch_large")
-            if not single:
-                self._sum_gradients()
-                self._custom_apply()
+            self._minibatch_call(lib.pc_ppo_minibatch_large, None, idx_all.data_ptr() + 8 * m * B, obs.data_ptr(), act.data_ptr(),
+                                 logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(), self._adv_stats.data_ptr() + 8 * m)
 
     def _epoch_body(self, idx_all, n_mb, args):
         """All minibatch steps of one epoch's update (train.py:223-261) with the hand-written kernels."""
@@ -563,9 +552,9 @@ class PPOLearner:
             return
         if self.diag_on:
             self.diag.zero_()      # sums and stop flag, at the head of every epoch and INSIDE the captured graph: a replay starts unstopped
-        if cfg.prepared_minibatches:
+        if self.prepared:
             pf = self.prepare_minibatches(idx_all, n_mb, *args)
-            if cfg.deferred_adam and not self.collective:
+            if self.chained:
                 self._epoch_chain(cfg.train_iters * n_mb)
                 return
             for m in range(cfg.train_iters * n_mb):
@@ -592,15 +581,11 @@ class PPOLearner:
         then costs the host one call, as on a single rank.  If this RCCL / driver refuses to capture a collective, say so once
         and fall back to eager enqueueing (identical results)."""
         g = torch.cuda.CUDAGraph()
-        if not self.collective:
+        if not self.collective or self.p2p is not None:      # plain kernels only (the one-shot exchange is one)
             with torch.cuda.graph(g):
                 self._epoch_body(idx_all, n_mb, args)
             return g
         import torch.distributed as dist
-        if self.p2p is not None:      # plain kernels only: captured like the single-rank update
-            with torch.cuda.graph(g):
-                self._epoch_body(idx_all, n_mb, args)
-            return g
         saved = [t.clone() for t in (self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.metrics)]
         try:
             dist.all_reduce(torch.zeros(1, device=self.device))       # the communicator exists before the capture starts
@@ -761,43 +746,49 @@ class PPOLearner:
             n_mb = self.n_minibatches
             idx_all = self.draw_indices(M)
         full = idx_all.shape[1] >= n_mb * B          # every minibatch has exactly B samples
-        if self.fused and full and getattr(self, "_f", None) is None:
-            self._fused_alloc(obs.shape[1], self.agent.actor[2].out_features)
         if self.large and not full:
             raise ValueError(f"large_minibatch: {M} samples do not fill {n_mb} minibatches of {B}")
-        if (self.custom or self.large) and full and not cfg.full_sweep:
-            # three tiny launches per minibatch, indices read in place from the epoch's index block; single rank +
-            # graphs: the whole epoch's update (train_iters x n_mb minibatches) is ONE captured graph
-            args = (obs, act, logprob, adv, ret)
-            if self.graphs and self._can_capture_update():
-                key = tuple(t.data_ptr() for t in args) + (M, idx_all.data_ptr())
-                if self._epoch_graph is None or self._epoch_key != key:
-                    torch.cuda.synchronize(self.device)
-                    if cfg.prepared_minibatches and not self.large:
-                        self.prepare_minibatches(idx_all, n_mb, *args)      # (allocates outside the capture)
-                        if getattr(self, "_state2", None) is None and cfg.deferred_adam and not self.collective:
-                            a1_, a2_ = self.agent.actor[0], self.agent.actor[2]
-                            self._state2 = torch.empty(lib.pc_ppo_epoch_state_floats(a1_.in_features, a1_.out_features, a2_.out_features),
-                                                       device=self.device)
-                        torch.cuda.synchronize(self.device)
-                    self._epoch_graph = self._capture_epoch(idx_all, n_mb, args)
-                    self._epoch_key = key
-                if self._epoch_graph is not None:
-                    self._epoch_graph.replay()
-                else:                                  # the capture of the collective was refused: eager from now on
-                    self._epoch_body(idx_all, n_mb, args)
-            else:
-                self._epoch_body(idx_all, n_mb, args)
-            self._opt_started = True
+        if self.path in ("custom", "large") and full and not cfg.full_sweep:
+            self._update_epoch_kernels(idx_all, n_mb, (obs, act, logprob, adv, ret))
+        else:
+            self._update_per_minibatch(idx_all, n_mb, full, obs, act, logprob, adv, ret)
+        self._opt_started = True
+        if self.flat_adam:
             self.lr_dev.mul_(cfg.learning_rate_decay)                                    # StepLR(step_size=1), :147,:269
-            return
+        else:
+            self.scheduler.step()                                                        # :269
+
+    def _update_epoch_kernels(self, idx_all, n_mb, args):
+        """The "custom" / "large" epoch: a few tiny launches per minibatch, indices read in place from the epoch's index block; with
+        graphs (and an exchange step that can be captured) the whole epoch's update, train_iters x n_mb minibatches, is ONE graph."""
+        if not (self.graphs and self._can_capture_update()):
+            return self._epoch_body(idx_all, n_mb, args)
+        key = tuple(t.data_ptr() for t in args) + (args[0].shape[0], idx_all.data_ptr())
+        if self._epoch_graph is None or self._epoch_key != key:
+            torch.cuda.synchronize(self.device)
+            if self.prepared:
+                self.prepare_minibatches(idx_all, n_mb, *args)      # (allocates outside the capture)
+                torch.cuda.synchronize(self.device)
+            self._epoch_graph = self._capture_epoch(idx_all, n_mb, args)
+            self._epoch_key = key
+        if self._epoch_graph is not None:
+            self._epoch_graph.replay()
+        else:                                  # the capture of the collective was refused: eager from now on
+            self._epoch_body(idx_all, n_mb, args)
+
+    def _update_per_minibatch(self, idx_all, n_mb, full, obs, act, logprob, adv, ret):
+        """The "torch" / "fused" epoch (and "custom" on ragged or full_sweep minibatches): one step per minibatch, as two replayed
+        graphs around the exchange where that can be captured."""
+        cfg, B = self.cfg, self.cfg.batch_size
+        if self.fused and full and self._f is None:
+            self._fused_alloc(obs.shape[1], self.agent.actor[2].out_features)
         # the torch-op step decides the stop on the host between its two halves: not from inside one captured graph
         use_graph = self.graphs and full and not (self.diag_on and not self.fused)
         if self.diag_on:
             self.diag.zero_()
         stopped = False
-        if use_graph and self._graph_key != (obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(),
-                                             ret.data_ptr(), M):
+        key = (obs.data_ptr(), act.data_ptr(), logprob.data_ptr(), adv.data_ptr(), ret.data_ptr(), obs.shape[0])
+        if use_graph and self._graph_key != key:
             self._build_graphs(obs, act, logprob, adv, ret)
         for it in range(cfg.train_iters):                                                # :223
             for mb in range(n_mb):                                                       # :228
@@ -817,11 +808,6 @@ class PPOLearner:
                     self.fused_minibatch_step(idx, obs, act, logprob, adv, ret)
                 else:
                     stopped = self.minibatch_step(obs[idx], act[idx], logprob[idx], adv[idx], ret[idx]) is False
-        self._opt_started = True
-        if self.fused:
-            self.lr_dev.mul_(cfg.learning_rate_decay)                                    # StepLR(step_size=1), :147,:269
-        else:
-            self.scheduler.step()                                                        # :269
 
 
 class Trainer:

@@ -119,6 +119,23 @@ def test_train_cli_accepts_the_flag():
     assert train.parse_args(["--run-name", "x"]).large_minibatch is False
 
 
+@pytest.mark.parametrize("kw", [dict(), dict(fused_update=False), dict(custom_mlp=False), dict(use_graphs=False), dict(prepared_minibatches=False),
+                                dict(deferred_adam=True), dict(force_collective=True), dict(full_sweep=True), dict(update_diagnostics=True),
+                                dict(target_kl=0.02), dict(target_kl=0.02, custom_mlp=False), dict(large_minibatch=True),
+                                dict(large_minibatch=True, batch_size=2056), dict(batch_size=2056)])
+def test_cpu_learner_plan_is_the_torch_path_with_the_legacy_attributes(kw):
+    """The update plan PPOLearner decides once (path, prepared, chained) and the attributes it is read through elsewhere: on the CPU
+    every configuration is the torch path, none of the kernel paths' attributes is set, and diag_on follows target_kl."""
+    cfg = PPOConfig(n_envs=4, n_steps=64, train_iters=1, **kw)
+    L = PPOLearner(Agent(18, 9), cfg, "cpu")
+    assert L.path == "torch" and not L.prepared and not L.chained
+    assert L.fused is False and L.custom is False and L.large is False and L.flat_adam is False and L.graphs is False
+    assert L.diag_on == (cfg.target_kl is not None or bool(kw.get("update_diagnostics")))
+    assert (L.diag is not None) == L.diag_on
+    assert L.collective == bool(kw.get("force_collective"))
+    assert isinstance(L.optimizer, torch.optim.Adam) and not hasattr(L, "exp_avg")
+
+
 def test_cpu_learner_is_the_torch_path_bit_for_bit():
     """On the CPU there are no kernels to take: the flag leaves the torch-op step exactly as it is (parameters, optimizer state,
     metrics, index draws)."""
