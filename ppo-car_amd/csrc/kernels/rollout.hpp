@@ -75,7 +75,7 @@ struct FastTabs {        // LDS addresses of the staged tables (wave-uniform)
 // the 33-ray big form has no 5.6 KB to spare and keeps one turn (the address is reduced mod 360 entries with two integer ops).
 constexpr int FT_HEAD = 0, FT_WRAP = FT_HEAD + 72 * 4, FT_ACT = FT_WRAP + 76, FT_GATES = FT_ACT + 16 * 8,
               FT_DIR = FT_GATES + TAB_MAX_GATES * 8, FT_RESET = FT_DIR + 720 * 4, FT_VTX = FT_RESET + 40,
-              FT_VTX_MAX = 64, FT_DIR64 = FT_VTX + FT_VTX_MAX * 12;   // (the vtx region holds 32-byte Vtx or 48-byte SegD records)
+              FT_DIR64 = FT_VTX + FT_VTX_MAX * 12;   // (the vtx region holds 32-byte Vtx or 48-byte SegD records)
 constexpr int FT_D64_BYTES = (FT_DIR64 - FT_DIR) * 4;
 __host__ __device__ constexpr int ft_seg_small(bool twice) { return FT_DIR64 + (twice ? 720 : 360) * 4; }
 __host__ __device__ constexpr int ft_floats(bool small, bool twice) { return ft_seg_small(twice) + (small ? FT_VTX_MAX * 12 : 0); }

@@ -1,6 +1,7 @@
 // ppocar.hip -- HIP kernels (gfx950 / CDNA4) and the C-ABI of libppocar.so.  ONE translation unit: the kernels live in
 // kernels/*.hpp (env_math, env_step, gae_sample, policy, rollout, update), included below in dependency order; this file
-// holds the host side (handles, launch configuration, the extern "C" entry points of include/ppocar.h).
+// holds the host side (handles, launch configuration, the extern "C" entry points of include/ppocar.h).  The track loader
+// (track_json.cpp) and the compiler of the tracks into the env kernels' tables (track_tables.cpp) are host-only units of their own.
 //
 // Kernels
 //   K1  env_step_kernel<T, RPL, MIXED>  the whole CarEnv.step transition (car_env.py:693-760) for one vector-env call,
@@ -63,7 +64,6 @@
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
-#include <unordered_set>
 #include <climits>
 #include <utility>
 #include <vector>
@@ -176,6 +176,35 @@ int pick_rpl(int need) {
     return -1;
 }
 
+// A device allocation that frees itself on destruction or reset (on the device that is current then: pc_env_destroy's guard).  upload =
+// allocate + copy from the host, from elements of the same size (the table compiler's plain pair types stand for double2 / float2);
+// nothing to upload leaves the buffer null.
+template <typename T> struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    hipError_t alloc(size_t n) {
+        reset();
+        return hipMalloc((void**)&p, n * sizeof(T));
+    }
+    template <typename H> hipError_t upload(const H* src, size_t n) {
+        static_assert(sizeof(H) == sizeof(T), "host and device elements of one layout");
+        reset();
+        if (!n) return hipSuccess;
+        const hipError_t rc = alloc(n);
+        return rc != hipSuccess ? rc : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    template <typename H> hipError_t upload(const std::vector<H>& v) { return upload(v.data(), v.size()); }
+    operator T*() const { return p; }
+};
+static_assert(sizeof(PairD) == sizeof(double2) && sizeof(PairF) == sizeof(float2), "the table compiler's pairs are the device's by layout");
+
 }  // namespace
 
 // pc_rollout's dispatch options: per env handle (pc_env_set_option).  There is no process-wide state: a new handle starts from
@@ -203,44 +232,37 @@ struct pc_env {
     int n_nominal = 12, R = 12, D = 18, n_tracks = 0;
     int lanes_override = 0;
     int lg = 0, rpl = 1, blocks = 0;
+    // the host-only parts of the compiled track tables (track_tables.cpp): the headers (start_collides filled in from the device), what
+    // dispatch needs to know of the batch's tracks, and -- further down -- the F64 rotation ids
     std::vector<TrackHdr> hdr_host;
-    // what dispatch needs to know of the batch's tracks, fixed once env_create_impl has built them.  The two layouts are the tracks'
-    // own: PC_OPT_ROLLOUT_FAST's nv28 switch (it can change after create) applies at dispatch.
-    struct TrackFacts {
-        int max_G = 0, max_nV = 0, sum_nV = 0;   // reward gates, chain vertices: of the largest track; chain vertices of all tracks together
-        bool tabs = true;    // every track has its gather tables (F64 handles: and the selector inside its limits and the rotation table)
-        bool rden = true;    // ... its 1/den table
-        bool sel = true;     // ... the selector inside its limits
-        bool nv28 = true;    // ... big_track's layout: two loops of 12 walls, a padded chain of 28 vertices
-        bool loops = true;   // ... two equal loops of 13 or of 9 chain vertices (big_track.json, track.json: 8 walls per loop)
-    } facts;
-    // device buffers
-    double4* pv = nullptr;
-    int4* iv = nullptr;
-    double* rot = nullptr;
-    uint8_t* track_id = nullptr;
+    TrackFacts facts;
+    // device buffers (each frees itself with the handle)
+    DevBuf<double4> pv;
+    DevBuf<int4> iv;
+    DevBuf<double> rot;
+    DevBuf<uint8_t> track_id;
     bool mixed = false;            // a track_id array was given (known before the geometry is chosen)
     bool track_blocks32 = false;   // mixed tracks: every aligned block of 32 envs holds ONE track (what pc_rollout needs)
     int track_block = 0;           // ... the largest of 256 / 128 / 64 / 32 for which that holds (0: none)
     bool track_bal64 = false, track_bal32 = false;   // two tracks, interleaved, every aligned block of 64 / 32 envs split evenly between them (and N a
                                                      // multiple of the block): the block's two waves de-interleave it (rollout_kernel's mode 7)
-    TrackHdr* hdr = nullptr;
-    Seg* segs = nullptr;
-    Vtx* vtx = nullptr;
-    VtxP* vtxp = nullptr;
-    double2* headtab = nullptr;
-    float2* dirtab = nullptr;
-    float* rden = nullptr;
-    double2* dirtab64 = nullptr;
-    SegD* seg64 = nullptr;
-    F64Dir* dirhash = nullptr;
+    DevBuf<TrackHdr> hdr;
+    DevBuf<Seg> segs;
+    DevBuf<Vtx> vtx;
+    DevBuf<VtxP> vtxp;
+    DevBuf<double2> headtab;
+    DevBuf<float2> dirtab;
+    DevBuf<float> rden;
+    DevBuf<double2> dirtab64;
+    DevBuf<SegD> seg64;
+    DevBuf<F64Dir> dirhash;
     std::vector<std::unordered_map<uint64_t, int>> rot_ids;   // F64, host only: per track, rotation bits -> row of the rotation table (pc_env_set_state)
     std::vector<std::vector<int>> rot_depth;                  // F64, host only: per track and row, how many turns from start_rot reach it
     int last_kernel = 0;           // PC_KERNEL_*: what the last successful pc_rollout launched (pc_env_last_rollout_kernel)
     int last_step_kernel = 0;      // PC_STEP_*: what the last pc_env_step / pc_env_step_many launched (pc_env_last_step_kernel)
     bool f64_offgrid = false;      // F64: pc_env_set_state left an env whose episode can leave the rotation table (a rotation that is not a
                                    // row, or a row more turns from start_rot than the env's time step): the selector kernel needs rows
-    float* reset_obs = nullptr;
+    DevBuf<float> reset_obs;
 
     template <typename T> EnvParams<T> params() const {
         EnvParams<T> p;
@@ -333,7 +355,7 @@ static int run_steps_fast(bool tab, int device, int blocks, size_t lds, hipStrea
 static int steps_fast_launch(pc_env* e, const int64_t* actions, int64_t T, double reward_scale, float* obs, float* reward, float* term,
                              float* trunc, bool table, hipStream_t st, int32_t* gates_passed = nullptr, float* final_obs = nullptr) {
     const bool f64 = e->dtype == PC_DTYPE_F64;
-    const pc_env::TrackFacts& f = e->facts;
+    const TrackFacts& f = e->facts;
     const bool rays12 = e->n_nominal == 12 && e->R == 12, rays16 = e->n_nominal == 16 && e->R == 17, rays32 = e->n_nominal == 32 && e->R == 33;
     if (!(rays12 || rays16 || rays32) || !e->opt.fast || T < 1 || T > INT_MAX) return PC_ERR_UNSUPPORTED;
     if ((gates_passed || final_obs) && T != 1) return PC_ERR_INVALID_ARG;      // (the optional outputs are pc_env_step's)
@@ -550,414 +572,59 @@ void pc_track_destroy(pc_track* t) { delete t; }
 void pc_env_destroy(pc_env* e) {
     if (!e) return;
     DeviceGuard g(e->device);
-    (void)hipFree(e->pv);
-    (void)hipFree(e->iv);
-    (void)hipFree(e->rot);
-    (void)hipFree(e->track_id);
-    (void)hipFree(e->hdr);
-    (void)hipFree(e->segs);
-    (void)hipFree(e->vtx);
-    (void)hipFree(e->vtxp);
-    (void)hipFree(e->headtab);
-    (void)hipFree(e->dirtab);
-    (void)hipFree(e->rden);
-    (void)hipFree(e->dirtab64);
-    (void)hipFree(e->seg64);
-    (void)hipFree(e->dirhash);
-    (void)hipFree(e->reset_obs);
-    delete e;
+    delete e;      // (the device buffers free themselves: DevBuf)
 }
 
-// glibc's cos and sin, each through its own call: an optimiser that sees both of one argument may merge them into sincos(), whose
-// cosine differs from cos() in the last place for some arguments -- and the tables below stand for the reference's separate
-// np.cos / np.sin calls (car_env.py:426-427, :584)
-__attribute__((noinline)) static double libm_cos(double a) { return std::cos(a); }
-__attribute__((noinline)) static double libm_sin(double a) { return std::sin(a); }
-
+// Compile the tracks and classify the track_id layout on the host (track_tables.cpp), upload the tables, and let the device fill in what
+// it computes by the kernels' own arithmetic: the 1/den table, each track's reset observation and start_collides.
 static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8_t* track_id) {
     const bool f64 = e->dtype == PC_DTYPE_F64;
-    // ---- host images of the track table
-    std::vector<Seg> segs;
-    std::vector<Vtx> vtx;
-    std::vector<VtxP> vtxp;
-    std::vector<F64Dir> dirhash;
-    std::vector<double2> headtab;
-    std::vector<float2> dirtab;
-    std::vector<double2> dirtab64;
-    std::vector<SegD> seg64;
-    std::vector<double2> vpos;      // host only: the chain vertices' exact positions (indexed like vtx)
-    size_t rden_floats = 0;
-    e->hdr_host.resize(e->n_tracks);
-    e->rot_ids.assign(e->n_tracks, {});
-    e->rot_depth.assign(e->n_tracks, {});
-    for (int k = 0; k < e->n_tracks; ++k) {
-        const pc_track* t = tracks[k];
-        TrackHdr& h = e->hdr_host[k];
-        h.S = t->n_walls();
-        h.G = t->n_gates();
-        h.n_scan = 0;
-        h.rot_off = -1;     // (F64 handles: set below)
-        h.n_rot = 0;
-        h.lat_off = -1;
-        h.sel_ok = 1;
-        h.wall_off = (int)segs.size();
-        for (size_t i = 0; i < t->walls.size(); i += 4) segs.push_back(Seg{t->walls[i], t->walls[i + 1], t->walls[i + 2], t->walls[i + 3]});
-        h.gate_off = (int)segs.size();
-        for (size_t i = 0; i < t->gates.size(); i += 4) segs.push_back(Seg{t->gates[i], t->gates[i + 1], t->gates[i + 2], t->gates[i + 3]});
-        // walls as vertex chains: a segment continues the chain iff it starts exactly where the previous ended.  The sweep's
-        // float32 coordinates are relative to the ANCHOR = the centre of the vertices' bounding box.
-        h.vtx_off = (int)vtx.size();
-        {
-            double bx0 = 1e300, bx1 = -1e300, by0 = 1e300, by1 = -1e300;
-            for (int w = 0; w < h.S; ++w) {
-                const Seg& sg = segs[h.wall_off + w];
-                bx0 = std::min({bx0, sg.x1, sg.x2}); bx1 = std::max({bx1, sg.x1, sg.x2});
-                by0 = std::min({by0, sg.y1, sg.y2}); by1 = std::max({by1, sg.y1, sg.y2});
-            }
-            h.ax0 = 0.5 * (bx0 + bx1);
-            h.ay0 = 0.5 * (by0 + by1);
-            h.bx0 = (float)bx0; h.bx1 = (float)bx1; h.by0 = (float)by0; h.by1 = (float)by1;
-        }
-        // the sweep's view of a wall's closing vertex: its anchor-relative position, the UNIT vector along (x1 - x2, y1 - y2)
-        // (car_env.py:171) in float32, and that vector's copy scaled by 2^-40
-        const auto edge = [&h](const Seg& sg) {
-            const double ex = sg.x1 - sg.x2, ey = sg.y1 - sg.y2, len = std::hypot(ex, ey);
-            const float xr = (float)(sg.x2 - h.ax0), yr = (float)(sg.y2 - h.ay0);
-            if (len == 0.0) return Vtx{xr, yr, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};     // a wall without length is never hit: a chain start
-            const float fx = (float)(ex / len), fy = (float)(ey / len);
-            return Vtx{xr, yr, fx, fy, fx * 0x1p-40f, fy * 0x1p-40f, 0.f, 0.f};
-        };
-        std::vector<int> wall_k(h.S);      // host only: wall w = the segment closed by chain vertex wall_k[w]
-        for (int w = 0; w < h.S; ++w) {
-            const Seg& sg = segs[h.wall_off + w];
-            const bool cont = w > 0 && segs[h.wall_off + w - 1].x2 == sg.x1 && segs[h.wall_off + w - 1].y2 == sg.y1;
-            if (!cont) {
-                vtx.push_back(Vtx{(float)(sg.x1 - h.ax0), (float)(sg.y1 - h.ay0), 0.f, 0.f, 1.f, 0.f, 0.f, 0.f});   // chain start: zero edge (scaled copy (1, 0): see Sweep::cand)
-                seg64.push_back(SegD{sg.x1, sg.y1, 0.0, 0.0, -1.0, 0, 0});
-                vpos.push_back(make_double2(sg.x1, sg.y1));
-            }
-            vtx.push_back(edge(sg));
-            seg64.push_back(SegD{sg.x1, sg.y1, sg.x1 - sg.x2, sg.y1 - sg.y2, -1.0, 0, 0});
-            vpos.push_back(make_double2(sg.x2, sg.y2));
-            wall_k[w] = (int)vtx.size() - 1 - h.vtx_off;
-        }
-        h.n_chain = (int)vtx.size() - h.vtx_off;
-        while ((vtx.size() - h.vtx_off) % 4) {  // the sweep walks vertex groups of four: pad with chain-start sentinels
-            vtx.push_back(Vtx{vtx.back().xr, vtx.back().yr, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f});
-            seg64.push_back(SegD{seg64.back().x1, seg64.back().y1, 0.0, 0.0, -1.0, 0, 0});
-            vpos.push_back(vpos.back());
-        }
-        h.nV = (int)vtx.size() - h.vtx_off;
-        // F32 mode: the selector's "nothing selected" pattern (SEL_INIT) carries vertex index 0 only while the index takes at
-        // most 13 of the candidate's mantissa bits; the float32 coordinates (relative to the track's anchor) and the flag
-        // thresholds are priced for a track that fits 2000 px.  F64 mode has neither limit.
-        if (h.nV > 65535 || (!f64 && h.nV > 8192)) {
-            g_hip_err = "track " + std::to_string(k) + ": " + std::to_string(h.nV) + " chain vertices; dtype f32 takes at most 8192 (use dtype f64)";
-            return PC_ERR_UNSUPPORTED;
-        }
-        if (!f64 && (h.bx1 - h.bx0 > 2000.0f || h.by1 - h.by0 > 2000.0f)) {
-            g_hip_err = "track " + std::to_string(k) + ": the walls' bounding box exceeds 2000 px; dtype f32 is priced for tracks that fit (use dtype f64)";
-            return PC_ERR_UNSUPPORTED;
-        }
-        // F64 handles: the float32 SELECTOR (the persistent kernel's literal form, env_step_fast<..., LIT>) runs on a track within
-        // those same limits; any other track takes the filter form (env_step_core<double>), which has none.
-        const bool sel = !f64 || (h.nV <= 8192 && h.bx1 - h.bx0 <= 2000.0f && h.by1 - h.by0 <= 2000.0f);
-        h.sel_ok = sel ? 1 : 0;
-        {   // low bits of a sweep candidate that carry the vertex index (at least 5: the unrolled 28-vertex sweep's constant)
-            int b = 5;
-            while ((1 << b) < h.nV) ++b;
-            h.idx_mask = (1u << b) - 1u;
-        }
-        // chain neighbours and end margins of every segment (SegD::h, SegD::prev_next), bounding box of the vertices
-        {
-            const int n = h.nV, o = h.vtx_off;
-            const auto is_start = [&](int k) { return seg64[o + k].ex == 0.0 && seg64[o + k].ey == 0.0; };
-            {   // exactly two chains?  (what the kernels compiled for big_track's layout rely on: TrackHdr::brk2)
-                int n_starts = 0, second = -1;
-                for (int k = 0; k < h.n_chain; ++k)
-                    if (is_start(k) && ++n_starts == 2) second = k;
-                h.brk2 = n_starts == 2 ? second : -1;
-                h.vtxp_off = -1;
-                if (h.brk2 > 0 && h.n_chain == 2 * h.brk2) {     // ... of the same length: the packed copy (VtxP)
-                    h.vtxp_off = (int)vtxp.size();
-                    for (int i = 0; i < h.brk2; ++i) {
-                        const Vtx &a = vtx[o + i], &b = vtx[o + h.brk2 + i];
-                        vtxp.push_back(VtxP{{a.xr, b.xr}, {a.yr, b.yr}, {a.ex, b.ex}, {a.ey, b.ey}, {a.exs, b.exs}, {a.eys, b.eys}});
-                    }
-                }
-            }
-            // What float32 can get wrong is the ORDER of two hits that lie within its resolution of each other.  The selector
-            // keeps 23 - b mantissa bits of a candidate (b index bits): two hits closer than sel_res = 1001 px * 2^-(23 - b) along
-            // a ray (beyond 1000 px the reported distance is 1000 either way) may be taken in the wrong order.
-            //   * Two walls that share a vertex V at an angle of at least ~13 degrees: such hits lie within sel_res / sin(13 deg) of
-            //     V, so a refined hit within `margin` = max(0.05 px, 4.6 sel_res) of a segment's end is compared with the chain
-            //     neighbours under the strict test (SegD::h; refine_careful).
-            //   * Anything else that brings two walls within `near` = max(0.05 px, 1.5 sel_res) of each other -- walls that cross
-            //     or touch without being chain neighbours (a T-junction, an X), a spike sharper than 13 degrees, a wall shorter than
-            //     2 margin (its neighbours' neighbours are that close) -- cannot be settled by looking at two neighbours: those
-            //     segments carry PC_SEG_SCAN and every ray whose selection lands on one of them is resolved by the float64 scan of
-            //     the whole chain under the reference's strict test (car_env.py:178), i.e. exactly.
-            int bits = 5;
-            while ((1 << bits) < h.nV) ++bits;
-            const double sel_res = 1001.0 * std::ldexp(1.0, -(23 - bits));
-            const double margin = std::max(0.05, 4.6 * sel_res), near = std::max(0.05, 1.5 * sel_res);
-            // (where the selector runs: nV <= 8192 there, so prev / next fit their 15 bits beside PC_SEG_SCAN; the F64 filter form never reads seg64)
-            for (int k = 0; k < n && sel; ++k) {
-                if (is_start(k)) continue;     // chain starts / padding: no segment (h = -1: |t - 0.5| < h never holds)
-                int c0 = k;     // first vertex of this chain, and its last
-                while (!is_start(c0)) --c0;
-                int c1 = k;
-                while (c1 + 1 < h.n_chain && !is_start(c1 + 1)) ++c1;
-                const bool closed = c1 > c0 && vpos[o + c0].x == vpos[o + c1].x && vpos[o + c0].y == vpos[o + c1].y;
-                const int prev = k - 1 > c0 ? k - 1 : (closed && c1 != k ? c1 : 0);       // shares this segment's first endpoint
-                const int next = k + 1 <= c1 ? k + 1 : (closed && c0 + 1 != k ? c0 + 1 : 0);   // shares its second endpoint
-                static_assert(PC_SEG_SCAN == 0x8000, "prev in bits 0..14, PC_SEG_SCAN in bit 15, next in bits 16..30");
-                seg64[o + k].prev_next = prev | (next << 16);      // (prev, next < nV <= 8192)
-                const double len = std::hypot(seg64[o + k].ex, seg64[o + k].ey);
-                seg64[o + k].h = 0.5 - margin / len;
-                if (len < 2.0 * margin) seg64[o + k].prev_next |= PC_SEG_SCAN;
-            }
-            if (sel) {
-                const auto seg_of = [&](int w) { return segs[h.wall_off + w]; };
-                const auto pt_seg = [](double px, double py, const Seg& s) {     // distance of a point from a segment
-                    const double ex = s.x2 - s.x1, ey = s.y2 - s.y1, l2 = ex * ex + ey * ey;
-                    double t = l2 > 0.0 ? ((px - s.x1) * ex + (py - s.y1) * ey) / l2 : 0.0;
-                    t = std::min(1.0, std::max(0.0, t));
-                    return std::hypot(px - (s.x1 + t * ex), py - (s.y1 + t * ey));
-                };
-                const auto orient = [](const Seg& s, double px, double py) { return (s.x2 - s.x1) * (py - s.y1) - (s.y2 - s.y1) * (px - s.x1); };
-                for (int a = 0; a < h.S; ++a) {
-                    const Seg sa = seg_of(a);
-                    const int ka = wall_k[a];
-                    if (is_start(ka)) continue;     // (a wall without length is a chain start: never hit)
-                    const int pa = seg64[o + ka].prev_next & 0x7fff, na = (int)(((unsigned)seg64[o + ka].prev_next >> 16) & 0x7fff);
-                    for (int b = a + 1; b < h.S; ++b) {
-                        const Seg sb = seg_of(b);
-                        const int kb = wall_k[b];
-                        if (is_start(kb)) continue;
-                        bool bad;
-                        if (pa == kb || na == kb) {
-                            // chain neighbours: a spike sharper than ~13 degrees (|sin| < 0.22 with the walls folding back on each other)
-                            const double ax = sa.x2 - sa.x1, ay = sa.y2 - sa.y1, bx = sb.x2 - sb.x1, by = sb.y2 - sb.y1;
-                            const double la = std::hypot(ax, ay), lb = std::hypot(bx, by);
-                            const double sn = std::fabs(ax * by - ay * bx) / (la * lb), cs = (ax * bx + ay * by) / (la * lb);
-                            // consecutive walls run head to tail: folding back = their directions nearly opposite
-                            bad = sn < 0.22 && cs < 0.0;
-                        } else {
-                            const double o1 = orient(sa, sb.x1, sb.y1), o2 = orient(sa, sb.x2, sb.y2), o3 = orient(sb, sa.x1, sa.y1), o4 = orient(sb, sa.x2, sa.y2);
-                            const bool cross = ((o1 > 0) != (o2 > 0)) && ((o3 > 0) != (o4 > 0));
-                            const double d = cross ? 0.0 : std::min({pt_seg(sa.x1, sa.y1, sb), pt_seg(sa.x2, sa.y2, sb), pt_seg(sb.x1, sb.y1, sa), pt_seg(sb.x2, sb.y2, sa)});
-                            bad = d < near;
-                        }
-                        if (bad) {
-                            seg64[o + ka].prev_next |= PC_SEG_SCAN;
-                            seg64[o + kb].prev_next |= PC_SEG_SCAN;
-                        }
-                    }
-                }
-                for (int k = 0; k < n; ++k)
-                    if (seg64[o + k].prev_next & PC_SEG_SCAN) { seg64[o + k].h = -1.0; ++h.n_scan; }
-            }
-            // F64 handles: the literal arithmetic wants the wall's SECOND ENDPOINT as the track file gives it (x1 - ex need not be
-            // x2 to the last bit): the records' (ex, ey) fields carry (x2, y2) from here on (lit_fast); a chain start or padding
-            // record gets x2 = x1: den == 0, never a hit
-            if (f64 && sel) {
-                for (int k = 0; k < n; ++k) {
-                    SegD& r = seg64[o + k];
-                    const bool start = is_start(k);
-                    r.ex = start ? r.x1 : vpos[o + k].x;
-                    r.ey = start ? r.y1 : vpos[o + k].y;
-                }
-            }
-        }
-        if (f64) {
-            // F64 mode: every angle an episode can reach (see Math<double>), glibc's cos / sin of it, hashed by the angle's bits
-            h.dir_off = -1;
-            h.head_off = 0;
-            h.rot_off = -1;
-            h.n_rot = 0;
-            if (e->n_tracks <= 16) {
-                std::unordered_set<uint64_t> rots, frontier, keys;
-                const auto bits = [](double v) { uint64_t b; std::memcpy(&b, &v, 8); return b; };
-                const auto val = [](uint64_t b) { double v; std::memcpy(&v, &b, 8); return v; };
-                std::vector<uint64_t> rot_list;                       // index -> rotation (breadth first; index 0 = start_rot: what reset gives)
-                std::unordered_map<uint64_t, int>& rid = e->rot_ids[k];
-                rid.clear();
-                std::vector<int>& depth = e->rot_depth[k];
-                int cur_depth = 0;
-                const auto add_rot = [&](uint64_t b) {
-                    if (!rots.insert(b).second) return false;
-                    rid[b] = (int)rot_list.size();
-                    rot_list.push_back(b);
-                    depth.push_back(cur_depth);
-                    return true;
-                };
-                add_rot(bits(t->start_rot));
-                frontier = rots;
-                for (int turn = 0; turn < 1000 && !frontier.empty(); ++turn) {      // CarEnv truncates at 1000 steps (car_env.py:749)
-                    cur_depth = turn + 1;
-                    std::unordered_set<uint64_t> next;
-                    for (const uint64_t b : frontier)
-                        for (const double w : {val(b) + 5.0, val(b) - 5.0})            // :440-442
-                            if (add_rot(bits(w))) next.insert(bits(w));
-                    frontier.swap(next);
-                }
-                {   // the rotation table (Math<double>): row i = the R rays' (cos, sin) at rotation i, then (index of rot - 5.0, index of rot + 5.0), then (rot, -)
-                    const int step_deg_ = 360 / e->n_nominal;
-                    h.rot_off = (int)dirtab64.size();
-                    h.n_rot = (int)rot_list.size();
-                    for (const uint64_t b : rot_list) {
-                        for (int ray = 0; ray < e->R; ++ray) {
-                            const double a = (val(b) + (double)(ray * step_deg_)) * (PC_PI / 180.0);   // np.radians(rot + a), :269, :465
-                            dirtab64.push_back(make_double2(libm_cos(a), libm_sin(a)));
-                        }
-                        const auto lk = rid.find(bits(val(b) - 5.0)), rk = rid.find(bits(val(b) + 5.0));
-                        dirtab64.push_back(make_double2(lk == rid.end() ? -1.0 : (double)lk->second, rk == rid.end() ? -1.0 : (double)rk->second));
-                        dirtab64.push_back(make_double2(val(b), 0.0));
-                    }
-                }
-                const int step_deg = 360 / e->n_nominal;
-                for (const uint64_t b : rots)
-                    for (int ray = 0; ray < e->R; ++ray) keys.insert(bits(val(b) + (double)(ray * step_deg)));   // :269, :465
-                size_t cap = 1024;
-                while (cap < 4 * keys.size()) cap <<= 1;
-                std::vector<F64Dir> tab;
-                for (;; cap <<= 1) {            // (grown until no probe sequence is longer than the device follows)
-                    tab.assign(cap, F64Dir{F64DIR_EMPTY, 0.0, 0.0, 0});
-                    bool ok = true;
-                    for (const uint64_t k : keys) {
-                        size_t slot = f64dir_hash(k) & (cap - 1);
-                        int probe = 0;
-                        while (tab[slot].key != F64DIR_EMPTY && probe < F64DIR_MAX_PROBE) { slot = (slot + 1) & (cap - 1); ++probe; }
-                        if (probe == F64DIR_MAX_PROBE) { ok = false; break; }
-                        const double a = val(k) * (PC_PI / 180.0);   // np.radians
-                        tab[slot] = F64Dir{k, libm_cos(a), libm_sin(a), 0};
-                    }
-                    if (ok) break;
-                }
-                h.dir_off = (int)dirhash.size();
-                h.head_off = (int)(cap - 1);
-                dirhash.insert(dirhash.end(), tab.begin(), tab.end());
-            }
-            if (dirtab64.empty()) dirtab64.push_back(make_double2(0.0, 0.0));
-            // the selector's float32 direction lattice (start_rot + j degrees: every angle rot + a is one of them mod 360; the float32
-            // direction only selects, so that cos of the unreduced angle differs in float64's last places does not matter)
-            h.lat_off = (int)dirtab.size();
-            for (int j = 0; j < 360; ++j) {
-                const double a = (t->start_rot + (double)j) * (PC_PI / 180.0);
-                dirtab.push_back(make_float2((float)libm_cos(a), (float)libm_sin(a)));
-            }
-            dirtab.push_back(make_float2(0.f, 0.f));
-        } else {
-            h.dir_off = (int)dirtab.size();
-            h.lat_off = h.dir_off;
-            for (int j = 0; j < 360; ++j) {  // direction lattice: start_rot + j degrees, np.radians then libm cos/sin
-                const double a = (t->start_rot + (double)j) * (PC_PI / 180.0);
-                dirtab.push_back(make_float2((float)libm_cos(a), (float)libm_sin(a)));
-                dirtab64.push_back(make_double2(libm_cos(a), libm_sin(a)));
-            }
-            dirtab.push_back(make_float2(0.f, 0.f));
-            dirtab64.push_back(make_double2(0.0, 0.0));
-        }
-        // the float32 1/den table [361][nV] exists only where a kernel can stage it in LDS: chains of at most FT_VTX_MAX vertices, and on F64
-        // handles only for tracks the selector may run on (a 65535-vertex float64 track would cost 95 MB it can never read)
-        const bool want_rden = h.nV <= FT_VTX_MAX && (!f64 || h.sel_ok);
-        if (rden_floats + (size_t)361 * h.nV > (size_t)INT_MAX) {
-            g_hip_err = "pc_env_create: the tracks' 1/den tables exceed 2^31 floats";
-            return PC_ERR_UNSUPPORTED;
-        }
-        h.rden_off = want_rden ? (int)rden_floats : -1;
-        if (want_rden) rden_floats += (size_t)361 * h.nV;
-        if (!f64) h.head_off = (int)headtab.size();
-        h.start_collides = 0;
-        h.start_x = t->start_x;
-        h.start_y = t->start_y;
-        h.start_rot = t->start_rot;
-        for (int j = 0; j < 72; ++j) {  // heading grid: start_rot + 5 j degrees, np.radians then libm cos/sin
-            const double a = (t->start_rot + 5.0 * j) * (PC_PI / 180.0);
-            headtab.push_back(make_double2(libm_cos(a), libm_sin(a)));
-        }
-    }
+    TrackTables tt;
+    const int rc = pc_internal_compile_tracks(tracks, e->n_tracks, e->n_nominal, e->R, e->dtype, tt, g_hip_err);
+    if (rc != PC_OK) return rc;
+    e->hdr_host = std::move(tt.hdr);
+    e->rot_ids = std::move(tt.rot_ids);
+    e->rot_depth = std::move(tt.rot_depth);
+    e->facts = tt.facts;
     // ---- device buffers
     const size_t N = (size_t)e->N;
-    HIPCHK(hipMalloc((void**)&e->pv, N * sizeof(double4)));
-    HIPCHK(hipMalloc((void**)&e->iv, N * sizeof(int4)));
-    if (f64) HIPCHK(hipMalloc((void**)&e->rot, N * sizeof(double)));
+    HIPCHK(e->pv.alloc(N));
+    HIPCHK(e->iv.alloc(N));
+    if (f64) HIPCHK(e->rot.alloc(N));
     if (track_id) {
-        for (int blk = 256; blk >= 32 && !e->track_block; blk >>= 1) {
-            bool ok = true;
-            for (size_t i = 0; i < N && ok; ++i) ok = track_id[i] == track_id[i & ~(size_t)(blk - 1)];
-            if (ok) e->track_block = blk;
-        }
-        e->track_blocks32 = e->track_block >= 32;
-        for (int blk = 64; blk >= 32; blk >>= 1) {
-            bool ok = e->n_tracks == 2 && N % blk == 0;
-            for (size_t b = 0; b < N && ok; b += blk) {
-                int ones = 0;
-                for (int i = 0; i < blk; ++i) ones += track_id[b + i] == 1, ok = ok && track_id[b + i] < 2;
-                ok = ok && ones == blk / 2;
-            }
-            (blk == 64 ? e->track_bal64 : e->track_bal32) = ok;
-        }
-        HIPCHK(hipMalloc((void**)&e->track_id, N));
-        HIPCHK(hipMemcpy(e->track_id, track_id, N, hipMemcpyHostToDevice));
+        const TrackLayout l = pc_internal_classify_track_ids(track_id, e->N, e->n_tracks);
+        e->track_block = l.track_block;
+        e->track_blocks32 = l.blocks32;
+        e->track_bal64 = l.bal64;
+        e->track_bal32 = l.bal32;
+        HIPCHK(e->track_id.upload(track_id, N));
     }
-    HIPCHK(hipMalloc((void**)&e->hdr, e->n_tracks * sizeof(TrackHdr)));
-    HIPCHK(hipMemcpy(e->hdr, e->hdr_host.data(), e->n_tracks * sizeof(TrackHdr), hipMemcpyHostToDevice));
-    static_assert(sizeof(Seg) == 32 && sizeof(Vtx) == 32, "segment / vertex records are 32 bytes (one s_load_dwordx8)");
-    HIPCHK(hipMalloc((void**)&e->segs, segs.size() * sizeof(Seg)));
-    HIPCHK(hipMemcpy(e->segs, segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&e->vtx, vtx.size() * sizeof(Vtx)));
-    HIPCHK(hipMemcpy(e->vtx, vtx.data(), vtx.size() * sizeof(Vtx), hipMemcpyHostToDevice));
-    static_assert(sizeof(VtxP) == 48, "packed vertex records: 48 bytes");
-    if (!vtxp.empty()) {
-        HIPCHK(hipMalloc((void**)&e->vtxp, vtxp.size() * sizeof(VtxP)));
-        HIPCHK(hipMemcpy(e->vtxp, vtxp.data(), vtxp.size() * sizeof(VtxP), hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc((void**)&e->headtab, headtab.size() * sizeof(double2)));
-    HIPCHK(hipMemcpy(e->headtab, headtab.data(), headtab.size() * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&e->dirtab, dirtab.size() * sizeof(float2)));
-    HIPCHK(hipMemcpy(e->dirtab, dirtab.data(), dirtab.size() * sizeof(float2), hipMemcpyHostToDevice));
-    static_assert(sizeof(SegD) == 48, "refinement table: 48 bytes per chain vertex");
-    HIPCHK(hipMalloc((void**)&e->dirtab64, dirtab64.size() * sizeof(double2)));
-    HIPCHK(hipMemcpy(e->dirtab64, dirtab64.data(), dirtab64.size() * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&e->seg64, seg64.size() * sizeof(SegD)));
-    HIPCHK(hipMemcpy(e->seg64, seg64.data(), seg64.size() * sizeof(SegD), hipMemcpyHostToDevice));
-    if (!dirhash.empty()) {
-        HIPCHK(hipMalloc((void**)&e->dirhash, dirhash.size() * sizeof(F64Dir)));
-        HIPCHK(hipMemcpy(e->dirhash, dirhash.data(), dirhash.size() * sizeof(F64Dir), hipMemcpyHostToDevice));
-    }
-    {
-        HIPCHK(hipMalloc((void**)&e->rden, (rden_floats ? rden_floats : 1) * sizeof(float)));
-        hipLaunchKernelGGL(rden_build_kernel, dim3(64), dim3(256), 0, 0, e->params<float>(), e->n_tracks, e->rden);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMalloc((void**)&e->reset_obs, (size_t)e->n_tracks * e->D * sizeof(float)));
+    HIPCHK(e->hdr.upload(e->hdr_host));
+    HIPCHK(e->segs.upload(tt.segs));
+    HIPCHK(e->vtx.upload(tt.vtx));
+    HIPCHK(e->vtxp.upload(tt.vtxp));
+    HIPCHK(e->headtab.upload(tt.headtab));
+    HIPCHK(e->dirtab.upload(tt.dirtab));
+    HIPCHK(e->dirtab64.upload(tt.dirtab64));
+    HIPCHK(e->seg64.upload(tt.seg64));
+    HIPCHK(e->dirhash.upload(tt.dirhash));
+    HIPCHK(e->rden.alloc(tt.rden_floats ? tt.rden_floats : 1));
+    hipLaunchKernelGGL(rden_build_kernel, dim3(64), dim3(256), 0, 0, e->params<float>(), e->n_tracks, e->rden.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(e->reset_obs.alloc((size_t)e->n_tracks * e->D));
     // ---- per-track reset observation + start_collides, computed on the device by the same arithmetic
-    int* d_sc = nullptr;
-    HIPCHK(hipMalloc((void**)&d_sc, e->n_tracks * sizeof(int)));
+    DevBuf<int> d_sc;
+    HIPCHK(d_sc.alloc(e->n_tracks));
     const int rb = (e->n_tracks + 63) / 64;
     if (f64)
-        hipLaunchKernelGGL(reset_obs_kernel<double>, dim3(rb), dim3(64), 0, 0, e->params<double>(), e->n_tracks, e->reset_obs, d_sc);
+        hipLaunchKernelGGL(reset_obs_kernel<double>, dim3(rb), dim3(64), 0, 0, e->params<double>(), e->n_tracks, e->reset_obs.p, d_sc.p);
     else
-        hipLaunchKernelGGL(reset_obs_kernel<float>, dim3(rb), dim3(64), 0, 0, e->params<float>(), e->n_tracks, e->reset_obs, d_sc);
+        hipLaunchKernelGGL(reset_obs_kernel<float>, dim3(rb), dim3(64), 0, 0, e->params<float>(), e->n_tracks, e->reset_obs.p, d_sc.p);
     HIPCHK(hipGetLastError());
     std::vector<int> sc(e->n_tracks);
     HIPCHK(hipMemcpy(sc.data(), d_sc, e->n_tracks * sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(d_sc);
     for (int k = 0; k < e->n_tracks; ++k) e->hdr_host[k].start_collides = sc[k];
     HIPCHK(hipMemcpy(e->hdr, e->hdr_host.data(), e->n_tracks * sizeof(TrackHdr), hipMemcpyHostToDevice));
-    pc_env::TrackFacts& tf = e->facts;
-    for (const TrackHdr& h : e->hdr_host) {
-        tf.max_G = std::max(tf.max_G, h.G);
-        tf.max_nV = std::max(tf.max_nV, h.nV);
-        tf.sum_nV += h.nV;
-        tf.tabs = tf.tabs && h.lat_off >= 0 && (!f64 || (h.sel_ok && h.rot_off >= 0));
-        tf.rden = tf.rden && h.rden_off >= 0;
-        tf.sel = tf.sel && h.sel_ok;
-        tf.nv28 = tf.nv28 && h.nV == 28 && h.n_chain == 26 && h.brk2 == 13 && h.vtxp_off >= 0;
-        tf.loops = tf.loops && h.vtxp_off >= 0 && (h.brk2 == 13 || h.brk2 == 9) && h.n_chain == 2 * h.brk2 && h.nV == 4 * ((h.brk2 + 1) / 2);
-    }
     return PC_OK;
 }
 
@@ -1090,7 +757,7 @@ int pc_env_info(pc_env* e, int32_t* gates_passed, int32_t* time_passed, void* st
     if (!e) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(env_info_kernel, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->iv, e->N, gates_passed,
+    hipLaunchKernelGGL(env_info_kernel, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->iv.p, e->N, gates_passed,
                        time_passed);
     HIPCHK(hipGetLastError());
     return PC_OK;
@@ -1589,7 +1256,7 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
     const bool lit = e->dtype == PC_DTYPE_F64;
     if (lit ? A != 9 : (A < 1 || A > 15)) return PC_ERR_UNSUPPORTED;
     const RolloutOpts& o = e->opt;
-    const pc_env::TrackFacts& f = e->facts;
+    const TrackFacts& f = e->facts;
     const bool all_nv28 = o.nv28 != 0 && f.nv28, all_loops = o.nv28 != 0 && f.loops;
     // mixed tracks interleaved inside a wave (no aligned block of 32 envs on one track; car_env.py:621-628 makes that legal): F32 handles
     // take the BIG form's generic mode, whose env step runs once per distinct track id of a wave (K1's waterfall), F64 handles the generic

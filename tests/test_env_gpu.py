@@ -16,6 +16,7 @@ import torch
 import oracle
 import ppo_car_amd as pc
 from conftest import ENV_CONFIGS, GOLDEN, TRACKS
+from junction_track import _junction_track_json
 
 pytestmark = pytest.mark.gpu
 
@@ -498,21 +499,6 @@ def test_f32_car_on_a_wall_line_and_rays_through_corners_match_the_oracle():
 # ------------------------------------------------------------------------------------------------
 # what F32 mode assumes of a track is CHECKED at pc_env_create (car_env.py:155-184 puts no constraint on the walls)
 # ------------------------------------------------------------------------------------------------
-def _junction_track_json(path):
-    """A box (outer loop) and an inner polyline T0 -> T1 -> A -> B -> C -> D whose first point lies in the INTERIOR of the box's
-    bottom wall (a T-junction: two walls touch without being chain neighbours) and whose segments AB and CD CROSS each other (an
-    X): both are outside what a float32 selector can order by looking at chain neighbours."""
-    import json
-    W, H = 1280.0, 720.0
-    n = lambda pts: [[x / W, y / H] for x, y in pts]
-    outer = [(50, 50), (650, 50), (650, 350), (50, 350), (50, 50)]
-    inner = [(300, 50), (300, 150), (420, 180), (520, 280), (520, 180), (420, 280)]
-    gates = [(60, 60), (61, 60), (70, 60), (71, 60)]
-    json.dump({"outer_track_points": n(outer), "inner_track_points": n(inner), "reward_gates": n(gates),
-               "initial_position": [150 / W, 200 / H], "initial_angle": 0.0}, open(path, "w"))
-    return path
-
-
 @pytest.mark.parametrize("n", [12, 16])
 def test_f32_t_junction_and_crossing_walls_match_the_oracle(tmp_path, n):
     """Cars on a fine grid around the T-junction's foot and around the crossing point, and on a coarse grid over the whole box:

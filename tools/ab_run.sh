@@ -12,7 +12,7 @@ if [ "$1" = "build" ]; then
   mkdir -p $d/ppo-car_amd $d/ppo_car_amd
   MIN=${AB_MIN:-1}; if [ "$MIN" != "0" ]; then MINFLAG="-DPC_DEV_MIN=$MIN"; else MINFLAG=""; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++20 -ffp-contract=off -Wno-unused-function -Iinclude -Ippo-car_amd/csrc $MINFLAG $3 -shared \
-      -o $d/ppo-car_amd/libppocar.so ppo-car_amd/csrc/ppocar.hip ppo-car_amd/csrc/track_json.cpp || exit 1
+      -o $d/ppo-car_amd/libppocar.so ppo-car_amd/csrc/ppocar.hip ppo-car_amd/csrc/track_json.cpp ppo-car_amd/csrc/track_tables.cpp || exit 1
   cp ppo-car_amd/*.py $d/ppo-car_amd/ && cp ppo_car_amd/__init__.py $d/ppo_car_amd/
   sed -i 's/^if lib.pc_build_ablate() != 0:/if False:/' $d/ppo-car_amd/_capi.py
   exit 0

@@ -10,7 +10,7 @@ if [ "$1" = "build" ]; then
     d=build/ablate_${n}_pkg
     mkdir -p $d/ppo-car_amd $d/ppo_car_amd
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -Wno-unused-function -Iinclude -Ippo-car_amd/csrc -DPC_ABLATE=$n -shared \
-        -o $d/ppo-car_amd/libppocar.so ppo-car_amd/csrc/ppocar.hip ppo-car_amd/csrc/track_json.cpp || exit 1
+        -o $d/ppo-car_amd/libppocar.so ppo-car_amd/csrc/ppocar.hip ppo-car_amd/csrc/track_json.cpp ppo-car_amd/csrc/track_tables.cpp || exit 1
     cp ppo-car_amd/*.py $d/ppo-car_amd/ && cp ppo_car_amd/__init__.py $d/ppo_car_amd/
     python3 - "$d/ppo-car_amd/_capi.py" <<'PY'
 import sys

@@ -7,7 +7,7 @@ OUT=${TMPDIR:-/tmp}/pc_res
 mkdir -p "$OUT"
 cd "$ROOT/ppo-car_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++20 -ffp-contract=off -I../../include -I. -shared -o "$OUT/lib_res.so" \
-    ppocar.hip track_json.cpp -Rpass-analysis=kernel-resource-usage 2> "$OUT/res.txt" || { tail -30 "$OUT/res.txt"; exit 1; }
+    ppocar.hip track_json.cpp track_tables.cpp -Rpass-analysis=kernel-resource-usage 2> "$OUT/res.txt" || { tail -30 "$OUT/res.txt"; exit 1; }
 python3 - "$OUT/res.txt" "${1:-rollout|env_step}" <<'PY'
 import re, subprocess, sys
 t = open(sys.argv[1]).read()

@@ -9,7 +9,7 @@ OUT=/tmp/pc_quick; mkdir -p $OUT; cd $OUT
 MASK=$1; shift
 if [ "$MASK" = "full" ]; then DEVFLAG=""; else DEVFLAG="-DPC_DEV_MIN=$MASK"; fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++20 -ffp-contract=off -Wno-unused-function -I$ROOT/include -I$ROOT/ppo-car_amd/csrc \
-    $DEVFLAG "$@" -shared -o $OUT/lib.so $ROOT/ppo-car_amd/csrc/ppocar.hip $ROOT/ppo-car_amd/csrc/track_json.cpp \
+    $DEVFLAG "$@" -shared -o $OUT/lib.so $ROOT/ppo-car_amd/csrc/ppocar.hip $ROOT/ppo-car_amd/csrc/track_json.cpp $ROOT/ppo-car_amd/csrc/track_tables.cpp \
     -Rpass-analysis=kernel-resource-usage 2> $OUT/res.txt || { grep -E "error|Error" -A5 $OUT/res.txt | head -60; exit 1; }
 python3 - $OUT/res.txt <<'PY'
 import re, subprocess, sys
