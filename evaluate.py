@@ -5,6 +5,8 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
 
     python evaluate.py --checkpoint checkpoints/<run>/model.dat --track tracks/big_track.json [--num-rays 12] [--episodes 5]
                        [--frames DIR [--frame-every 5]]      # PNG frames of episode 0 (software rasteriser, no pygame)
+    python evaluate.py --checkpoint ... --envs 4096 [--greedy]       # batched: the first episodes of 4096 envs (ppo_car_amd.Evaluator),
+                                                                     # JSON with the eval/* scalars (lap times in steps) and the path taken
 """
 import argparse
 import json
@@ -22,10 +24,14 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--frames", default=None, help="directory for PNG frames of episode 0 (the role of log_video's frames)")
     ap.add_argument("--frame-every", type=int, default=5)
+    ap.add_argument("--envs", type=int, default=None, help="batched evaluation: the first episodes of this many envs on the device "
+                    "(ppo_car_amd.Evaluator) instead of the --episodes loop; prints the eval/* scalars")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs the GPU: the env has no CPU path")
     import ppo_car_amd as pc
+    if args.envs is not None:
+        return batched(pc, args)
     torch.manual_seed(args.seed)
     env = pc.VecCarEnv(args.episodes, args.track, num_rays=args.num_rays, reward_scaling=1.0, device="cuda")
     agent = pc.Agent(env.obs_dim, env.act_dim).cuda()
@@ -68,6 +74,22 @@ def main(argv=None):
            "mean_gates_passed": float(gates.float().mean()), "returns": ret.tolist(), "gates_passed": gates.tolist()}
     if args.frames:
         out["frames"] = frames
+    print(json.dumps(out))
+    return out
+
+
+def batched(pc, args):
+    """--envs N: N first episodes in 1000 device steps, no host round trip per step."""
+    from ppo_car_amd.env import ray_count
+    agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
+    agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
+    ev = pc.Evaluator(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda", greedy=args.greedy,
+                      seed=args.seed)
+    try:
+        out = ev.evaluate()
+        out["path"] = ev.last_path
+    finally:
+        ev.close()
     print(json.dumps(out))
     return out
 

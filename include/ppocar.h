@@ -238,6 +238,36 @@ int pc_gae_bootstrap(int device, const float* rew, const float* val, const float
 int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, uint64_t offset, int64_t* actions,
               float* logprob, float* entropy, void* stream);
 
+/* ---- batched evaluation (opt-in: the entry points above are untouched): the FIRST episode of every env and its lap times, and the
+ * deterministic action.  What the reference's log_video answers with one fresh episode (train.py:23-50) and every PPO library with
+ * evaluate_policy: N fresh episodes from the start line, one per env.
+ * pc_first_episodes: a FORWARD scan over rew, term, trunc [T][N] float32 in pc_episode_stats' two layouts (PC_EPISODE_BUFFER: step t's
+ *   flags in row t + 1, step T - 1's in last_term / last_trunc [N]; PC_EPISODE_STEPS: flags[t] belong to rew[t], last_* are not read
+ *   and may be NULL).  state [PC_FIRST_ROWS][N] float64 (device, in / out; the caller initialises rows 0-5 to 0 and rows 6-7 to +inf):
+ *     row 0  return of the first episode: the float64 sum of the float32 (scaled) rewards -- exact (kernels/gae_sample.hpp: an episode
+ *            has at most PC_TIME_LIMIT steps), so the bits are those of a forward sum in any grouping
+ *     row 1  length in steps            row 2  gates, row 3  laps (decoded as pc_episode_stats does: k = rint(r / reward_scale))
+ *     row 4  status: PC_FIRST_RUNNING, PC_FIRST_TERMINATED or PC_FIRST_TRUNCATED (both flags on the closing step: terminated)
+ *     row 5  the episode's step count at its last lap close (0 = no lap yet) = the sum of its lap times
+ *     row 6  best lap in steps: the steps between consecutive lap closes, the first lap from the episode's start; +inf = none
+ *     row 7  first lap in steps; +inf = none
+ *   An env whose status is not RUNNING on entry is left untouched; after the step that closes its episode the rest of the window is
+ *   ignored.  Windows chain: one call over T rows and any split of the same rows into consecutive calls leave the same state bits.
+ *   Checked before any device call, in pc_episode_stats' order: NULL rew / term / trunc / state, T < 1, N < 1, a layout other than
+ *   the two, NULL last_* in the Buffer layout, a reward_scale pc_episode_stats refuses: PC_ERR_INVALID_ARG; then device < 0 or
+ *   unknown: PC_ERR_NO_DEVICE.  Never synchronises.
+ * pc_greedy: for logits [N][A] float32 (finite), actions[i] = the FIRST index of the maximum of row i (torch.argmax's tie rule);
+ *   action_f32 [N] = its float copy, or NULL; logprob [N] = log_softmax(logits[i])[actions[i]] in pc_sample's arithmetic (the bits
+ *   pc_sample gives for that action), or NULL.  It sits behind pc_policy_act(..., logits_out): the policy kernels have no greedy mode.
+ *   NULL logits / actions or N < 1: PC_ERR_INVALID_ARG (checked before any device call); A < 1 or A > 16: PC_ERR_UNSUPPORTED. */
+#define PC_FIRST_ROWS 8
+#define PC_FIRST_RUNNING 0
+#define PC_FIRST_TERMINATED 1
+#define PC_FIRST_TRUNCATED 2
+int pc_first_episodes(int device, const float* rew, const float* term, const float* trunc, const float* last_term,
+                      const float* last_trunc, int64_t T, int64_t N, int layout, double reward_scale, double* state, void* stream);
+int pc_greedy(int device, const float* logits, int64_t N, int A, int64_t* actions, float* action_f32, float* logprob, void* stream);
+
 /* ---- the whole of Agent.get_action_and_value(x) as the rollout calls it (model.py:34-41, train.py:181):
  * both 1-hidden-layer MLPs (actor D->H->A, critic D->H->1, ReLU), the categorical draw, log_prob and the
  * value, in one launch on the matrix cores.  A policy step's configuration is a HANDLE: shape (D, H, A), arithmetic form of the

@@ -17,6 +17,8 @@ PC_ERR_INVALID_ARG, PC_ERR_IO, PC_ERR_PARSE, PC_ERR_HIP, PC_ERR_UNSUPPORTED, PC_
 PC_XCHG_HANDLE_BYTES = 128
 PC_DTYPE_F32, PC_DTYPE_F64 = 0, 1
 PC_EPISODE_BUFFER, PC_EPISODE_STEPS = 0, 1
+PC_FIRST_ROWS = 8        # pc_first_episodes: rows of the per-env state (include/ppocar.h)
+PC_FIRST_RUNNING, PC_FIRST_TERMINATED, PC_FIRST_TRUNCATED = 0, 1, 2
 PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppocar.h)
 PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_TIME_LIMIT = 1000     # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
@@ -86,6 +88,8 @@ _sig = {
     "pc_gae_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_gae_bootstrap": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_sample": (_i, [_i, _vp, _i64, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pc_first_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp]),
+    "pc_greedy": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "pc_policy_create": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pc_policy_destroy": (None, [_vp]),
     "pc_policy_get": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),

@@ -1,5 +1,5 @@
 // ppocar.hip -- HIP kernels (gfx950 / CDNA4) and the C-ABI of libppocar.so.  ONE translation unit: the kernels live in
-// kernels/*.hpp (env_math, env_step, gae_sample, policy, rollout, update), included below in dependency order; this file
+// kernels/*.hpp (env_math, env_step, gae_sample, evaluation, policy, rollout, update), included below in dependency order; this file
 // holds the host side (handles, launch configuration, the extern "C" entry points of include/ppocar.h).  The track loader
 // (track_json.cpp) and the compiler of the tracks into the env kernels' tables (track_tables.cpp) are host-only units of their own.
 //
@@ -22,6 +22,8 @@
 //                                       persistent launch (large / small batches)
 //   K10-12 ppo_fwdbwd / grad_reduce / adam (+ clip_adam_mb, the multi-rank step)   one PPO minibatch step without any library GEMM
 //   K13 xchg_allreduce_kernel          the per-minibatch gradient all-reduce as a one-shot exchange over peer-mapped buffers (pc_xchg_*)
+//   K14 first_episodes_kernel<STEPS>   the forward scan of the batched evaluation: each env's first episode and its lap times (pc_first_episodes)
+//   K15 greedy_kernel                  argmax action + its log_prob, the deterministic sibling of K4 (pc_greedy)
 //
 // Work decomposition of K1: an env is owned by G = 2^lg consecutive lanes of one
 // wavefront ("lanes per env", chosen on the host from n_envs so the chip is filled); lane g of the
@@ -74,6 +76,7 @@
 #include "kernels/env_math.hpp"
 #include "kernels/env_step.hpp"
 #include "kernels/gae_sample.hpp"
+#include "kernels/evaluation.hpp"
 #include "kernels/policy.hpp"
 #include "kernels/rollout.hpp"
 #include "kernels/env_steps.hpp"
@@ -950,6 +953,36 @@ int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, 
     const int blocks = (int)((N + 255) / 256);
     hipLaunchKernelGGL(sample_kernel<16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, N, A, seed, offset, actions,
                        logprob, entropy);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_first_episodes(int device, const float* rew, const float* term, const float* trunc, const float* last_term,
+                      const float* last_trunc, int64_t T, int64_t N, int layout, double reward_scale, double* state, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!rew || !term || !trunc || !state || T < 1 || N < 1) return PC_ERR_INVALID_ARG;
+    if (layout != PC_EPISODE_BUFFER && layout != PC_EPISODE_STEPS) return PC_ERR_INVALID_ARG;
+    if (layout == PC_EPISODE_BUFFER && (!last_term || !last_trunc)) return PC_ERR_INVALID_ARG;
+    if (!valid_reward_scale(reward_scale)) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const auto k = layout == PC_EPISODE_STEPS ? first_episodes_kernel<true> : first_episodes_kernel<false>;
+    hipLaunchKernelGGL(k, dim3((int)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, term, trunc, last_term, last_trunc, T, N,
+                       1.0 / reward_scale, state);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_greedy(int device, const float* logits, int64_t N, int A, int64_t* actions, float* action_f32, float* logprob, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!logits || !actions || N < 1) return PC_ERR_INVALID_ARG;
+    if (A < 1 || A > 16) return PC_ERR_UNSUPPORTED;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    hipLaunchKernelGGL(greedy_kernel<16>, dim3((int)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, N, A, actions,
+                       action_f32, logprob);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }

@@ -26,6 +26,7 @@ from ._capi import PC_TIME_LIMIT, check, lib
 from .buffer import Buffer
 from .env import VecCarEnv
 from .episodes import EpisodeStats, episode_scalars
+from .evaluation import EVAL_TOTALS, Evaluator
 from .model import Agent
 
 
@@ -114,8 +115,19 @@ class PPOConfig:
                                            # grid of workgroups that walk the samples, no library GEMM).  Needs fused_update, custom_mlp, the standard
                                            # 256-wide MLPs and full minibatches; not with update_diagnostics / target_kl, deferred_adam or full_sweep.
                                            # batch_size <= 1024: accepted, changes nothing
+    eval_every: int = 0                    # > 0: every eval_every-th epoch run_epoch adds the eval/* keys -- the FIRST episode of eval_envs fresh
+                                           # envs from the start line under the updated policy, with lap times (ppo_car_amd.Evaluator: its own
+                                           # env handle, weight image and random stream; training computes the same bits with it on or off).
+                                           # Rank 0 only.  0 = off: not one launch is added to an epoch
+    eval_envs: int = 1024                  # envs (= episodes) per evaluation
+    eval_greedy: bool = False              # argmax actions (pc_greedy) instead of draws
+    eval_track: str | list | None = None   # the track(s) evaluated on; None = `track` (with track_interleave); another file = a held-out track
 
     def __post_init__(self):
+        if self.eval_every < 0:
+            raise ValueError(f"PPOConfig.eval_every must be >= 0 (0 = off), not {self.eval_every!r}")
+        if self.eval_envs < 1:
+            raise ValueError(f"PPOConfig.eval_envs must be >= 1, not {self.eval_envs!r}")
         if self.truncation_bootstrap not in ("reference", "final_obs"):
             raise ValueError(f"PPOConfig.truncation_bootstrap must be 'reference' or 'final_obs', not {self.truncation_bootstrap!r}")
         if self.target_kl is not None:
@@ -139,6 +151,16 @@ class PPOConfig:
             if self.full_sweep:
                 raise ValueError("PPOConfig.large_minibatch cannot be combined with full_sweep (its indices are drawn on the device, "
                                  "outside the epoch's index block)")
+
+
+def mixed_track_ids(tracks, n_envs, interleave):
+    """Each env's track for a list of tracks: env i runs track (i * n_tracks) // n_envs, rounded to blocks of 32 envs (the layout the
+    persistent rollout kernel accepts), or i % n_tracks when interleaved.  None for a single track."""
+    if not (isinstance(tracks, (list, tuple)) and len(tracks) > 1):
+        return None
+    i = np.arange(n_envs)
+    nt = len(tracks)
+    return (i % nt if interleave else np.minimum((i // 32 * 32) * nt // n_envs, nt - 1)).astype(np.uint8)
 
 
 def flatten_parameters(module):
@@ -817,12 +839,7 @@ class Trainer:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         torch.manual_seed(cfg.seed)  # identical initial parameters on every rank (then broadcast anyway)
-        track_id = None
-        if isinstance(cfg.track, (list, tuple)) and len(cfg.track) > 1:
-            import numpy as np
-            i = np.arange(cfg.n_envs)
-            nt = len(cfg.track)
-            track_id = (i % nt if cfg.track_interleave else np.minimum((i // 32 * 32) * nt // cfg.n_envs, nt - 1)).astype(np.uint8)
+        track_id = mixed_track_ids(cfg.track, cfg.n_envs, cfg.track_interleave)
         self.envs = VecCarEnv(cfg.n_envs, cfg.track, num_rays=cfg.num_rays, reward_scaling=cfg.reward_scaling,
                               device=self.device, dtype=cfg.env_dtype, track_id=track_id)
         self.obs_dim = (self.envs.obs_dim,)          # train.py:141
@@ -876,6 +893,16 @@ class Trainer:
             self._final_step = torch.zeros(N, *self.obs_dim, device=self.device)
             self._fv_act = torch.empty(N, dtype=torch.int64, device=self.device)
             self._fv_logprob = torch.empty(N, device=self.device)
+        # eval_every: the evaluator lives on rank 0 (replicas are bit-identical: no collective, no other rank waits).  Its seed differs from
+        # every rank's rng_seed; its stream position is the epoch, so a resumed run evaluates exactly as the uninterrupted one
+        self.evaluator = None
+        if cfg.eval_every > 0 and rank == 0 and self.device.type == "cuda":
+            ev_track = cfg.track if cfg.eval_track is None else cfg.eval_track
+            self.evaluator = Evaluator(self.agent, ev_track, n_envs=cfg.eval_envs, num_rays=cfg.num_rays, reward_scaling=cfg.reward_scaling,
+                                       device=self.device, dtype=cfg.env_dtype,
+                                       track_id=mixed_track_ids(ev_track, cfg.eval_envs, cfg.track_interleave),
+                                       greedy=cfg.eval_greedy, seed=cfg.seed * 1000003 + 0x9E3779B9,
+                                       rollout_kernel="steps" if cfg.rollout_kernel == "steps" else "auto")
 
     # ---- train.py:173-195 ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -1046,6 +1073,10 @@ class Trainer:
             ev[2].record()
             self.phase_events.append(ev)
         self.epoch += 1
+        ev_tot = None                 # float64 [EVAL_TOTALS], still on the device
+        if self.evaluator is not None and self.epoch % self.cfg.eval_every == 0:
+            self.evaluator.run(index=self.epoch)
+            ev_tot = self.evaluator.totals()
         if not sync:
             return None
         if sync == "lazy" and self.world_size == 1 and self.device.type == "cuda":
@@ -1064,9 +1095,13 @@ class Trainer:
             if ep_tot is not None:      # the episode totals in float64, next to the seven floats
                 host_ep = torch.empty(7, dtype=torch.float64, pin_memory=True)
                 host_ep.copy_(ep_tot, non_blocking=True)
+            host_ev = None
+            if ev_tot is not None:
+                host_ev = torch.empty(EVAL_TOTALS, dtype=torch.float64, pin_memory=True)
+                host_ev.copy_(ev_tot, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            self._pending_scalars = (host, done, self.global_step_idx, host_ep)
+            self._pending_scalars = (host, done, self.global_step_idx, host_ep, host_ev)
             return prev
         self.flush_scalars()        # (a switch from lazy to synchronous calls drops nothing silently: the pending epoch is waited for)
         self.check_exchange()       # (synchronises; the scalars below are fetched anyway) a timed-out exchange stops the job HERE
@@ -1093,6 +1128,8 @@ class Trainer:
             out.update(episode_scalars(ep_tot.tolist(), self.cfg.reward_scaling))
         if self.learner.diag_on:
             diag_scalars(self.learner.diag.tolist(), float(self._ev_out[4].to(torch.float32)), out)
+        if ev_tot is not None:
+            out.update(self.evaluator.scalars(ev_tot.tolist()))
         return out
 
     def flush_scalars(self):
@@ -1100,7 +1137,7 @@ class Trainer:
         pend, self._pending_scalars = getattr(self, "_pending_scalars", None), None
         if pend is None:
             return None
-        host, done, gstep, host_ep = pend
+        host, done, gstep, host_ep, host_ev = pend
         done.synchronize()
         m = host.tolist()
         lr = m[5]
@@ -1114,6 +1151,8 @@ class Trainer:
             out.update(episode_scalars(host_ep.tolist(), self.cfg.reward_scaling))
         if len(m) > 7:
             diag_scalars(m[7:7 + _capi.PC_DIAG_FLOATS], m[7 + _capi.PC_DIAG_FLOATS], out)
+        if host_ev is not None:
+            out.update(self.evaluator.scalars(host_ev.tolist()))
         return out
 
     # ---- checkpoint / resume (the reference only saves agent.state_dict(), train.py:283,301) ----
@@ -1169,3 +1208,5 @@ class Trainer:
             if self.learner.p2p is not None:
                 self.learner.p2p.close()
             self.envs.close()
+            if self.evaluator is not None:
+                self.evaluator.close()

@@ -13,3 +13,4 @@ from .env import Track, VecCarEnv  # noqa: E402,F401
 from .buffer import Buffer  # noqa: E402,F401
 from .episodes import EpisodeStats  # noqa: E402,F401
 from .model import Agent, PolicyRangeError, layer_init  # noqa: E402,F401
+from .evaluation import Evaluator  # noqa: E402,F401

@@ -64,6 +64,11 @@ def parse_args(argv=None):
                    "1.5 x this (Stable-Baselines3's target_kl; implies --update-diagnostics)")
     p.add_argument("--large-minibatch", action="store_true", help="--batch-size above 1024: the hand-written large-minibatch update kernels "
                    "instead of the torch-op step (PPOConfig.large_minibatch; changes nothing up to 1024)")
+    p.add_argument("--eval-every", type=int, default=0, help="every this many epochs, evaluate the updated policy on the first episodes of "
+                   "--eval-envs fresh envs and log eval/* (return, length, gates, laps, crash rate, lap times in steps); 0 = off")
+    p.add_argument("--eval-envs", type=int, default=1024, help="envs (= episodes) per evaluation")
+    p.add_argument("--eval-greedy", action="store_true", help="evaluate with argmax actions instead of draws")
+    p.add_argument("--eval-track", default=None, help="track JSON to evaluate on (default: --track; another file = a held-out track)")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -108,7 +113,8 @@ def main(argv=None):
                     policy_precision={"fp16x2": 2, "bf16x3": 1, "fp32": 0}[args.policy_arith], policy_range=args.policy_range,
                     episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap,
                     update_diagnostics=args.update_diagnostics, target_kl=args.target_kl,
-                    large_minibatch=args.large_minibatch)
+                    large_minibatch=args.large_minibatch, eval_every=args.eval_every, eval_envs=args.eval_envs,
+                    eval_greedy=args.eval_greedy, eval_track=args.eval_track)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
@@ -129,6 +135,11 @@ def main(argv=None):
             if "losses/approx_kl" in scalars:
                 line += (f"KL {scalars['losses/approx_kl']:.5f}, clipfrac {scalars['losses/clipfrac']:.3f}, explained variance "
                          f"{scalars['losses/explained_variance']:.3f}, {scalars['charts/update_steps']} update steps. ")
+            if scalars.get("eval/episodic_return") is not None:
+                lap = scalars["eval/best_lap_steps"]
+                line += (f"Eval: return {scalars['eval/episodic_return']:.3f}, length {scalars['eval/episodic_length']:.1f}, laps "
+                         f"{scalars['eval/laps_per_episode']:.3f}, crash rate {scalars['eval/crash_rate']:.3f}, best lap "
+                         + (f"{lap:.0f} steps. " if lap is not None else "none. "))
             print(line, flush=True)
             log.write(json.dumps(scalars) + "\n")
             log.flush()
