@@ -7,6 +7,7 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
                        [--frames DIR [--frame-every 5]]      # PNG frames of episode 0 (software rasteriser, no pygame)
     python evaluate.py --checkpoint ... --envs 4096 [--greedy]       # batched: the first episodes of 4096 envs (ppo_car_amd.Evaluator),
                                                                      # JSON with the eval/* scalars (lap times in steps) and the path taken
+    python evaluate.py --checkpoint ... --envs 4096 --greedy --rollout-kernel mega     # ... the greedy windows as persistent launches
 """
 import argparse
 import json
@@ -14,7 +15,7 @@ import json
 import torch
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", required=True, help="agent state_dict as train.py saves it (checkpoint_<n>.dat / model.dat)")
     ap.add_argument("--track", default="tracks/big_track.json")
@@ -26,7 +27,14 @@ def main(argv=None):
     ap.add_argument("--frame-every", type=int, default=5)
     ap.add_argument("--envs", type=int, default=None, help="batched evaluation: the first episodes of this many envs on the device "
                     "(ppo_car_amd.Evaluator) instead of the --episodes loop; prints the eval/* scalars")
-    args = ap.parse_args(argv)
+    ap.add_argument("--rollout-kernel", choices=("auto", "mega", "steps"), default="auto",
+                    help="--envs: how the Evaluator steps -- 'mega' = persistent launches (pc_rollout; with --greedy pc_rollout_greedy), 'steps' = "
+                    "the per-step kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs the GPU: the env has no CPU path")
     import ppo_car_amd as pc
@@ -84,7 +92,7 @@ def batched(pc, args):
     agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
     agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     ev = pc.Evaluator(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda", greedy=args.greedy,
-                      seed=args.seed)
+                      seed=args.seed, rollout_kernel=args.rollout_kernel)
     try:
         out = ev.evaluate()
         out["path"] = ev.last_path

@@ -258,7 +258,8 @@ int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, 
  *   unknown: PC_ERR_NO_DEVICE.  Never synchronises.
  * pc_greedy: for logits [N][A] float32 (finite), actions[i] = the FIRST index of the maximum of row i (torch.argmax's tie rule);
  *   action_f32 [N] = its float copy, or NULL; logprob [N] = log_softmax(logits[i])[actions[i]] in pc_sample's arithmetic (the bits
- *   pc_sample gives for that action), or NULL.  It sits behind pc_policy_act(..., logits_out): the policy kernels have no greedy mode.
+ *   pc_sample gives for that action), or NULL.  It sits behind pc_policy_act(..., logits_out) for callers that hold logits; pc_policy_act_greedy / pc_rollout_greedy
+ *   (below) take the argmax inside the policy step itself.
  *   NULL logits / actions or N < 1: PC_ERR_INVALID_ARG (checked before any device call); A < 1 or A > 16: PC_ERR_UNSUPPORTED. */
 #define PC_FIRST_ROWS 8
 #define PC_FIRST_RUNNING 0
@@ -310,6 +311,13 @@ int pc_policy_pack_checked(const pc_policy* p, const float* aW1, const float* ab
 int pc_policy_act(const pc_policy* p, const float* obs, int64_t N, const float* image, uint64_t seed, uint64_t offset,
                   const uint64_t* offset_dev, int64_t* action, float* action_f32, float* logprob, float* value, float* logits_out,
                   void* stream);
+/* pc_policy_act's GREEDY form: the same policy step with action [i] = the FIRST index of the maximum logit of row i (float equality: -0.0
+ * and +0.0 tie and the lower index wins -- torch.argmax's rule and pc_greedy's; logits are finite by contract) in place of the draw.  No seed,
+ * offset or offset_dev: no random number is generated.  logits_out and value carry pc_policy_act's bits on the same inputs; logprob [i] =
+ * logit[action] - logsumexp in the kernel's own arithmetic, i.e. the bits pc_policy_act writes wherever it draws that action.  Every form a
+ * policy handle can have (precision 0 / 1 / 2, split or not, A = 1 .. 15).  Argument checks, their order and the status codes: pc_policy_act's. */
+int pc_policy_act_greedy(const pc_policy* p, const float* obs, int64_t N, const float* image, int64_t* action, float* action_f32,
+                         float* logprob, float* value, float* logits_out, void* stream);
 
 /* ---- the whole rollout of one epoch (train.py:173-195) as ONE persistent launch: for t in 0..T-1
  *   (action, logprob, value) = Agent.get_action_and_value(obs_t)      [pc_policy_act's arithmetic and RNG, offset + t]
@@ -366,6 +374,19 @@ int pc_rollout_final_obs(pc_env* e, const pc_policy* p, const float* image, int6
                          uint64_t offset, const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf,
                          float* term_buf, float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc,
                          float* last_value, float* reward_sum, float* final_obs, int64_t slots, void* stream);
+/* The GREEDY rollout (what evaluate_policy(deterministic=True) steps): T x (pc_policy_act_greedy; pc_env_step) as one persistent launch, bit for
+ * bit, in every buffer pc_rollout fills.  final_obs == NULL: pc_rollout's outputs (`slots` is ignored); else pc_rollout_final_obs's, with its
+ * `slots` check.  The other argument checks are pc_rollout's.  The launch is the greedy instance of the kernel pc_rollout picks for the same
+ * handle and options -- same PC_KERNEL_* id, envs per workgroup, grid, LDS bytes and 1/den-table choice -- where that kernel is on the greedy
+ * menu: F32 handles, fp16 x 2 policy arithmetic (precision 2), Discrete(9), 12 / 16 / 32 nominal rays, the table-driven modes (small form, big
+ * form, 16-envs-per-wave form).  Everything else -- F64 handles, precision 0 and 1, the generic mode (PC_OPT_ROLLOUT_FAST = 0, ray counts or
+ * tracks off the fast menu), tracks interleaved inside a block of 32 envs, A != 9 -- is PC_ERR_UNSUPPORTED before any device call, with
+ * pc_env_last_rollout_kernel unchanged: callers then run the two per-step kernels, as for pc_rollout's refusals. */
+int pc_rollout_greedy(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale,
+                      float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
+                      float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term,
+                      float* next_trunc, float* last_value, float* reward_sum,
+                      float* final_obs, int64_t slots, void* stream);
 
 /* ---- the non-GEMM work of one PPO minibatch step (train.py:230-261), three launches:
  * pc_ppo_gather : traj_*[batch_indices] (train.py:233-238,249): idx [B] int64 into the flattened trajectories

@@ -96,8 +96,10 @@ _sig = {
     "pc_policy_pack": (_i, [_vp] + [_vp] * 8 + [_vp, _vp]),
     "pc_policy_pack_checked": (_i, [_vp] + [_vp] * 8 + [_vp, _vp, _vp]),
     "pc_policy_act": (_i, [_vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _vp] + [_vp] * 5 + [_vp]),
+    "pc_policy_act_greedy": (_i, [_vp, _vp, _i64, _vp] + [_vp] * 5 + [_vp]),
     "pc_rollout": (_i, [_vp, _vp, _vp, _i64, _d, C.c_uint64, C.c_uint64, _vp] + [_vp] * 12 + [_vp]),
     "pc_rollout_final_obs": (_i, [_vp, _vp, _vp, _i64, _d, C.c_uint64, C.c_uint64, _vp] + [_vp] * 12 + [_vp, _i64, _vp]),
+    "pc_rollout_greedy": (_i, [_vp, _vp, _vp, _i64, _d] + [_vp] * 12 + [_vp, _i64, _vp]),
     "pc_env_set_option": (_i, [_vp, _i, _i]),
     "pc_env_get_option": (_i, [_vp, _i, C.POINTER(_i)]),
     "pc_ppo_gather": (_i, [_i, _vp, _i, _i] + [_vp] * 10 + [_vp]),

@@ -233,6 +233,7 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
 // (idx, offset >> 2) and key `seed` -- all four words of a block are used, so a kernel that walks consecutive
 // offsets (the persistent rollout) runs the ten rounds once per four draws.
 struct PhiloxBlock { uint32_t w[4]; };
+struct NoPhilox {};     // what stands in the block's place in a kernel's greedy instance: no registers
 __device__ __forceinline__ PhiloxBlock philox_block(uint64_t seed, uint64_t block, uint64_t idx) {
     uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)block, (uint32_t)(block >> 32)};
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);

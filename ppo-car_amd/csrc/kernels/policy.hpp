@@ -619,6 +619,40 @@ __device__ __forceinline__ void policy_tail(const float (&v)[16], const int A_rt
         if (logits_row) logits_row[i] = v[i];
     }
 }
+// The GREEDY form of policy_tail (pc_policy_act_greedy): mx, the exponentials, their sum and lse exactly as above -- the same
+// operations in the same order --, then act = the FIRST index whose logit equals the maximum (float equality: -0.0 and +0.0 tie and the
+// lower index wins; torch.argmax's rule and pc_greedy's) and lp = v[act] - lse: the bits policy_tail returns whenever it draws that
+// action.  No uniform: the caller generates no Philox block.  (Logits are finite by contract; the last index takes whatever is not.)
+template <int AC = 0>
+__device__ __forceinline__ void policy_tail_greedy(const float (&v)[16], const int A_rt, int& act, float& lp, float& val,
+                                                   float* __restrict__ logits_row) {
+    const int A = AC > 0 ? AC : A_rt;
+    float mx = -INFINITY;
+    val = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i == A) val = v[i];
+        if (i < A) mx = fmaxf(mx, v[i]);
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i >= A) break;
+        sum += softmax_exp(v[i] - mx);
+    }
+    const float lse = mx + softmax_log(sum);
+    lp = 0.0f;
+    act = -1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i >= A) break;
+        if (act < 0 && (v[i] == mx || i == A - 1)) {
+            act = i;
+            lp = v[i] - lse;
+        }
+        if (logits_row) logits_row[i] = v[i];
+    }
+}
 
 // The same draw for Discrete(9) (car_env.py:525) on the TWO lanes that own an env (lane = 2 env + g: the env step's mapping, so the
 // action never leaves the lane pair): lane 0 holds logits 0..3 and the value (output 9), lane 1 logits 4..8 -- four / five
@@ -659,6 +693,40 @@ __device__ __forceinline__ void policy_tail_pair(const float (&w)[5], const int 
     const int n_other = __builtin_amdgcn_update_dpp(0, n, 0xb1, 0xf, 0xf, false);
     const int n_lo = hi ? n_other : n, n_hi = hi ? n : n_other;
     act = n_lo < 4 ? n_lo : 4 + (n_hi < 4 ? n_hi : 4);               // last bin absorbs rounding
+    const int li = act - (hi ? 4 : 0);                               // index among this lane's logits (if it is this lane's)
+    float mine = l[0];
+#pragma unroll
+    for (int j = 1; j < 5; ++j) mine = li == j ? l[j] : mine;
+    mine -= lse;
+    const float theirs = dpp_swap_pair_f(mine);
+    lp = ((act >= 4) == hi) ? mine : theirs;
+    const float v_other = dpp_swap_pair_f(w[4]);
+    val = hi ? v_other : w[4];
+}
+// The GREEDY form of policy_tail_pair: mx, sum and lse as above, then the first index of the maximum -- each lane finds the first of ITS
+// logits that equals the pair's maximum (lane 0: indices 0..3, lane 1: 4..8), lane 0 wins a tie between the two.  lp = logit[act] - lse
+// through the selection above: the bits policy_tail_pair returns whenever it draws that action.  No uniform.
+__device__ __forceinline__ void policy_tail_pair_greedy(const float (&w)[5], const int g, int& act, float& lp, float& val) {
+    const bool hi = g != 0;
+    float l[5];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) l[j] = w[j];
+    l[4] = hi ? w[4] : -INFINITY;                  // lane 0's fifth output is the value, not a logit
+    float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
+    mx = fmaxf(mx, l[4]);
+    mx = fmaxf(mx, dpp_swap_pair_f(mx));
+    float ex[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) ex[j] = softmax_exp(l[j] - mx);     // (exp2(-inf) = 0 for lane 0's fifth slot)
+    const float part = (((ex[0] + ex[1]) + ex[2]) + ex[3]) + ex[4];
+    const float sum = part + dpp_swap_pair_f(part);
+    const float lse = mx + softmax_log(sum);
+    int n = 5;                                                       // the first of this lane's logits at the maximum (5: none)
+#pragma unroll
+    for (int j = 4; j >= 0; --j) n = l[j] == mx ? j : n;
+    const int n_other = __builtin_amdgcn_update_dpp(0, n, 0xb1, 0xf, 0xf, false);
+    const int n_lo = hi ? n_other : n, n_hi = hi ? n : n_other;
+    act = n_lo < 4 ? n_lo : 4 + (n_hi < 4 ? n_hi : 4);               // (finite logits: one of the two lanes holds the maximum)
     const int li = act - (hi ? 4 : 0);                               // index among this lane's logits (if it is this lane's)
     float mine = l[0];
 #pragma unroll
@@ -716,6 +784,30 @@ __device__ __forceinline__ void policy_tail_row(const float v, const int i, cons
     lp = __shfl(l, row0 + act, 64) - lse;
     val = __shfl(v, row0 + A, 64);
 }
+// The GREEDY form of policy_tail_row: mx, sum and lse as above, then a ballot of `l == mx` inside the 16-lane row, whose lowest set bit is
+// the first index of the maximum.  lp = logit[act] - lse: the bits policy_tail_row returns whenever it draws that action.  No uniform.
+__device__ __forceinline__ void policy_tail_row_greedy(const float v, const int i, const int A, const int lane, int& act, float& lp,
+                                                       float& val) {
+    const float l = i < A ? v : -INFINITY;
+    float mx = l;
+    mx = fmaxf(mx, PC_ROW_ROR(mx, 8));
+    mx = fmaxf(mx, PC_ROW_ROR(mx, 4));
+    mx = fmaxf(mx, PC_ROW_ROR(mx, 2));
+    mx = fmaxf(mx, PC_ROW_ROR(mx, 1));
+    const float ex = i < A ? softmax_exp(l - mx) : 0.0f;
+    float sum = ex;
+    sum += PC_ROW_ROR(sum, 8);
+    sum += PC_ROW_ROR(sum, 4);
+    sum += PC_ROW_ROR(sum, 2);
+    sum += PC_ROW_ROR(sum, 1);
+    const float lse = mx + softmax_log(sum);
+    const unsigned long long at_max = __ballot(i < A && l == mx);
+    const unsigned row = (unsigned)(at_max >> (lane & 48)) & 0xffffu;
+    act = row ? __builtin_ctz(row) : A - 1;                                // (finite logits: some lane of the row holds the maximum)
+    const int row0 = lane & 48;
+    lp = __shfl(l, row0 + act, 64) - lse;
+    val = __shfl(v, row0 + A, 64);
+}
 #undef PC_ROW_ROR
 #undef PC_ROW_SHR0
 
@@ -746,7 +838,8 @@ template <int NDW> __device__ __forceinline__ void policy_stage_image(const floa
 //                batch that cannot fill the chip with 256-env workgroups (n_envs < ~32 k) finishes in a
 //                fraction of the single-pass latency of the other form.
 // PREC = 0: fp32-input MFMA (bit-for-bit an fp32 fmaf chain).  PREC = 1: bf16x3 split on the bf16 matrix cores.
-template <int KS, bool SPLIT, int PREC>
+// GREEDY (pc_policy_act_greedy): the argmax tails in place of the draws -- seed / offset / offset_dev are not read, no Philox block is generated.
+template <int KS, bool SPLIT, int PREC, bool GREEDY = false>
 __global__ __launch_bounds__(512) void policy_kernel(const float* __restrict__ obs, const int64_t N, const int D, const int A,
                                                      const float* __restrict__ image, const uint64_t seed, const uint64_t offset,
                                                      const uint64_t* __restrict__ offset_dev, int64_t* __restrict__ action,
@@ -771,7 +864,8 @@ __global__ __launch_bounds__(512) void policy_kernel(const float* __restrict__ o
     policy_stage_image<IMG>(image, lds, tid);
     __syncthreads();
 
-    const uint64_t off = offset + (offset_dev ? *offset_dev : 0);
+    uint64_t off = 0;
+    if constexpr (!GREEDY) off = offset + (offset_dev ? *offset_dev : 0);
     float* myOut = sOut + wave * 32 * LDO;
     const int ht0 = SPLIT ? wave * (NT / 8) : 0, ht1 = SPLIT ? ht0 + NT / 8 : NT;
     const int64_t n_chunks = (N + ENVS_PER_WG - 1) / ENVS_PER_WG;
@@ -844,7 +938,8 @@ __global__ __launch_bounds__(512) void policy_kernel(const float* __restrict__ o
             const float t = __builtin_fmaf(ps, PolScale<PREC>::so_inv, sB2[oi]);   // outputs back from their scaled domain
             int act;
             float lp, val;
-            policy_tail_row(t, oi, A, philox_uniform(seed, off, (uint64_t)e), lane, act, lp, val);
+            if constexpr (GREEDY) policy_tail_row_greedy(t, oi, A, lane, act, lp, val);
+            else policy_tail_row(t, oi, A, philox_uniform(seed, off, (uint64_t)e), lane, act, lp, val);
             if (e < N) {
                 if (logits_out && oi < A) logits_out[e * A + oi] = t;
                 if (oi == 0) {
@@ -862,7 +957,8 @@ __global__ __launch_bounds__(512) void policy_kernel(const float* __restrict__ o
                 pair_outputs<LDO>(myOut, row, g, PolScale<PREC>::so_inv, sB2, w);
                 int act;
                 float lp, val;
-                policy_tail_pair(w, g, philox_uniform(seed, off, (uint64_t)e), act, lp, val);
+                if constexpr (GREEDY) policy_tail_pair_greedy(w, g, act, lp, val);
+                else policy_tail_pair(w, g, philox_uniform(seed, off, (uint64_t)e), act, lp, val);
                 if (logits_out) {
 #pragma unroll
                     for (int j = 0; j < 5; ++j)
@@ -883,7 +979,8 @@ __global__ __launch_bounds__(512) void policy_kernel(const float* __restrict__ o
                 for (int i = 0; i < 16; ++i) v[i] = __builtin_fmaf(myOut[lane * LDO + i], PolScale<PREC>::so_inv, sB2[i]);   // outputs back from their scaled domain
                 int act;
                 float lp, val;
-                policy_tail(v, A, philox_uniform(seed, off, (uint64_t)e), act, lp, val, logits_out ? logits_out + e * A : nullptr);
+                if constexpr (GREEDY) policy_tail_greedy(v, A, act, lp, val, logits_out ? logits_out + e * A : nullptr);
+                else policy_tail(v, A, philox_uniform(seed, off, (uint64_t)e), act, lp, val, logits_out ? logits_out + e * A : nullptr);
                 action[e] = act;
                 if (action_f) action_f[e] = (float)act;
                 logprob[e] = lp;

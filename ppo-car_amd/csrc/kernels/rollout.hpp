@@ -938,7 +938,9 @@ __device__ __forceinline__ EnvParams<float> stage_tables(const EnvParams<float>&
 //         where 32-env waves leave every SIMD with a single wave (9.8 us per step whatever the batch): two 16-env waves per SIMD
 //         hide each other's latency.  More vector instructions per env (the per-wave work -- physics, draw, bookkeeping -- is shared
 //         by 16 envs, not 32), so it loses again where 32-env waves already come in pairs (above 32768 envs).  Same bits.
-template <int KS, int RPL, int PREC, int MODE, bool LIT = false, int LGE = 1>
+//         GREEDY (pc_rollout_greedy; the table-driven modes of F32 handles, fp16 x 2, Discrete(9)): the argmax tail in place of the draw --
+//         seed / offset / offset_dev are not read, no Philox block is generated, the block's registers do not exist.
+template <int KS, int RPL, int PREC, int MODE, bool LIT = false, int LGE = 1, bool GREEDY = false>
 __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, const float* __restrict__ image, const int A,
                                                       const int T, const double reward_scale, const uint64_t seed,
                                                       const uint64_t offset, const uint64_t* __restrict__ offset_dev,
@@ -954,6 +956,7 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
     constexpr int GE = 1 << LGE, EPWV = 64 / GE;      // lanes per env, envs per wave
     constexpr int HID = 256, NT = 2 * HID / 16, LD1 = pol_ld1(KS), ET = EPWV / 16;
     static_assert(LGE == 1 || (LGE == 2 && MODE != 0 && PREC != 0), "16 envs per wave: fast modes, split operand forms");
+    static_assert(!GREEDY || (MODE >= 1 && MODE <= 5 && PREC == 2 && !LIT), "the greedy menu: F32 handles, fp16 x 2, the single-track table-driven modes");
     constexpr int NG = pol_ng(KS), KB = pol_kb(KS);
     constexpr int IMG = PREC ? polx_image_dwords(PREC, NG) : pol_image_padded(KS);
     constexpr bool FAST = MODE != 0;
@@ -1056,8 +1059,9 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
     static_assert(4 * KS + 1 >= 20, "the output tile must fit the wave's observation rows");
     static_assert(LGE == 1 || DC >= LDO, "the output tile [16 envs][LDO] must fit the wave's 16 observation rows");
     float* myOut = sObs + wave * EPWV * LDX;
-    const uint64_t off0 = offset + (offset_dev ? *offset_dev : 0);
-    PhiloxBlock rnd = {};  // the sampling lanes' current Philox block (4 steps' draws)
+    uint64_t off0 = 0;
+    if constexpr (!GREEDY) off0 = offset + (offset_dev ? *offset_dev : 0);
+    [[maybe_unused]] std::conditional_t<GREEDY, NoPhilox, PhiloxBlock> rnd = {};  // the sampling lanes' current Philox block (4 steps' draws)
     // FAST: per-lane invariants of the env step.  Ray slot s of lane g is ray min(g + 2 s, R - 1): the odd slot that 17 or
     // 33 rays leave over on lane 1 repeats that lane pair's last ray (same value, same address) instead of being masked.
     int gq[2] = {0, 0}, k72 = 0;
@@ -1190,12 +1194,15 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
                     // (four lanes per env: lanes 2, 3 repeat lanes 0, 1 -- the same values, the action in all four)
                     pair_outputs<LDO>(myOut, lane >> LGE, g & 1, PolScale<PREC>::so_inv, sB2, w);
                     float lp, val;
+                    if constexpr (!GREEDY) {
                     if (t == 0 || (o & 3) == 0) {   // uniform: ten rounds per 4 steps
                         uint64_t ctr = (uint64_t)e_env;             // (opaque: the first round's products of the lane's counter are formed here,
                         asm volatile("" : "+v"(ctr));               // not hoisted into four registers that live through all T steps)
                         rnd = philox_block(seed, o >> 2, ctr);
                     }
+                    }
                     if constexpr (PC_ABLATE & 4) { act_reg = (int)(o & 7); lp = w[0]; val = w[4]; }
+                    else if constexpr (GREEDY) policy_tail_pair_greedy(w, g & 1, act_reg, lp, val);
                     else policy_tail_pair(w, g & 1, philox_word_uniform(rnd, (unsigned)(o & 3)), act_reg, lp, val);
                     if constexpr (!FAST) { if (g == 0) sAct[el] = act_reg; }
                     if (g == 0) {
@@ -1224,8 +1231,11 @@ __global__ __launch_bounds__(512) void rollout_kernel(const EnvParams<float> p, 
                     for (int i = 0; i < 16; ++i) v[i] = __builtin_fmaf(myOut[lane * LDO + i], PolScale<PREC>::so_inv, sB2[i]);   // outputs back from their scaled domain
                     int act;
                     float lp, val;
-                    if (t == 0 || (o & 3) == 0) rnd = philox_block(seed, o >> 2, (uint64_t)e);  // uniform: ten rounds per 4 steps
-                    policy_tail(v, A, philox_word_uniform(rnd, (unsigned)(o & 3)), act, lp, val, nullptr);
+                    if constexpr (GREEDY) policy_tail_greedy(v, A, act, lp, val, nullptr);
+                    else {
+                        if (t == 0 || (o & 3) == 0) rnd = philox_block(seed, o >> 2, (uint64_t)e);  // uniform: ten rounds per 4 steps
+                        policy_tail(v, A, philox_word_uniform(rnd, (unsigned)(o & 3)), act, lp, val, nullptr);
+                    }
                     sAct[pbase + lane] = act;
                     if (tail) {
                         last_val[e] = val;
@@ -1578,7 +1588,8 @@ __global__ __launch_bounds__(512) void rollout_f64_kernel(const EnvParams<double
 // MODE as in rollout_kernel: 0 = generic tables, env_step_core; 1 / 2 = single track, A = 9, every table in LDS behind LDS
 // pointers, env_step_fast (2: with the 1/den table), dense observation rows copied out by three waves in 16-byte stores.
 // LIT: the handle is PC_DTYPE_F64 -- env_step_wave's / env_step_fast's literal form, state with the rotation's row of the rotation table.
-template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false>
+// GREEDY: as in rollout_kernel (policy_tail_row_greedy in place of the row draw).
+template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false, bool GREEDY = false>
 __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<float> p, const float* __restrict__ image, const int A,
                                                             const int T, const double reward_scale, const uint64_t seed,
                                                             const uint64_t offset, const uint64_t* __restrict__ offset_dev,
@@ -1600,6 +1611,7 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
     constexpr bool FAST = MODE != 0;
     constexpr int DC = RPL == 3 ? 18 : (RPL == 5 ? 23 : 39);   // FAST: 6 + the ray count the 4-lanes-per-env menu implies (12 / 17 / 33)
     static_assert(EPW == 32 || (EPW == 16 && FAST && PREC != 0 && DC <= 23), "16 envs per workgroup: fast mode, split operand forms, <= 17 rays");
+    static_assert(!GREEDY || (FAST && PREC == 2 && !LIT), "the greedy menu: F32 handles, fp16 x 2, the table-driven modes");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* sW1 = lds;
     float* sB1 = PREC ? lds + polx_w1_dwords(PREC, NG) + polx_w2_dwords(PREC) : sW1 + 2 * HID * LD1;
@@ -1670,8 +1682,9 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
     }
     float* myOut = sOut + wave * EPW * LDO;
     const int ht0 = wave * (NT / 8), ht1 = ht0 + NT / 8;
-    const uint64_t off0 = offset + (offset_dev ? *offset_dev : 0);
-    PhiloxBlock rnd = {};  // the sampling lanes' current Philox block (4 steps' draws)
+    uint64_t off0 = 0;
+    if constexpr (!GREEDY) off0 = offset + (offset_dev ? *offset_dev : 0);
+    [[maybe_unused]] std::conditional_t<GREEDY, NoPhilox, PhiloxBlock> rnd = {};  // the sampling lanes' current Philox block (4 steps' draws)
     int gq[2] = {0, 0}, k72 = 0;
     FastLane fl = {};
     if constexpr (FAST) {
@@ -1779,10 +1792,17 @@ __global__ __launch_bounds__(512) void rollout_small_kernel(const EnvParams<floa
             for (int w = 0; w < 8; ++w) ps += sOut[(w * EPW + dl) * LDO + oi];  // fixed order
             const float tsum = __builtin_fmaf(ps, PolScale<PREC>::so_inv, sB2[oi]);   // outputs back from their scaled domain
             const uint64_t o = off0 + (uint64_t)t;
-            if (t == 0 || (o & 3) == 0) rnd = philox_block(seed, o >> 2, (uint64_t)e);  // uniform: ten rounds per 4 steps
+            if constexpr (!GREEDY) {
+                if (t == 0 || (o & 3) == 0) rnd = philox_block(seed, o >> 2, (uint64_t)e);  // uniform: ten rounds per 4 steps
+            }
             float lp, val;
-            if (!(dbg & 4)) policy_tail_row(tsum, oi, A, philox_word_uniform(rnd, (unsigned)(o & 3)), lane, act, lp, val);
-            else { act = 0; lp = tsum; val = tsum; }
+            if constexpr (GREEDY) {
+                if (!(dbg & 4)) policy_tail_row_greedy(tsum, oi, A, lane, act, lp, val);
+                else { act = 0; lp = tsum; val = tsum; }
+            } else {
+                if (!(dbg & 4)) policy_tail_row(tsum, oi, A, philox_word_uniform(rnd, (unsigned)(o & 3)), lane, act, lp, val);
+                else { act = 0; lp = tsum; val = tsum; }
+            }
             if (oi == 0 && e < N) {
                 if constexpr (!WOWN) sAct[dl] = act;
                 if (tail) {

@@ -420,15 +420,15 @@ static int step_generic_launch(pc_env* e, const int64_t* actions, double reward_
 
 // policy_kernel's arguments, handed by policy_act_impl to the instance it picks (`split`: the SPLIT instance)
 using PolicyArgs = std::tuple<const float*, int64_t, int, int, const float*, uint64_t, uint64_t, const uint64_t*, int64_t*, float*, float*, float*, float*>;
-template <int KS, int PREC>
+template <int KS, int PREC, bool GR = false>
 static int run_policy(bool split, int device, int blocks, size_t lds, hipStream_t st, const PolicyArgs& args) {
     return std::apply([&](auto... a) {
-        return split ? launch_lds<policy_kernel<KS, true, PREC>>(device, blocks, lds, st, a...)
-                     : launch_lds<policy_kernel<KS, false, PREC>>(device, blocks, lds, st, a...);
+        return split ? launch_lds<policy_kernel<KS, true, PREC, GR>>(device, blocks, lds, st, a...)
+                     : launch_lds<policy_kernel<KS, false, PREC, GR>>(device, blocks, lds, st, a...);
     }, args);
 }
-template <int PREC>
-static auto policy_run_for(int KS) { return KS == 5 ? run_policy<5, PREC> : KS == 6 ? run_policy<6, PREC> : run_policy<10, PREC>; }
+template <int PREC, bool GR = false>
+static auto policy_run_for(int KS) { return KS == 5 ? run_policy<5, PREC, GR> : KS == 6 ? run_policy<6, PREC, GR> : run_policy<10, PREC, GR>; }
 
 // one pc_rollout call's arguments, as the rollout kernels take them
 struct RolloutIO {
@@ -454,21 +454,22 @@ struct RolloutPlan {
     int kernel = 0;     // PC_KERNEL_*: what pc_env_last_rollout_kernel reports
 };
 
-template <int KS, int RPL, int PREC, int MODE, bool LIT = false, int LGE = 1>
+// (GR: the kernel's greedy instance -- pc_rollout_greedy; the call's seed / offset are zeros it does not read)
+template <int KS, int RPL, int PREC, int MODE, bool LIT = false, int LGE = 1, bool GR = false>
 static int roll_big(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, hipStream_t st) {
     EnvParams<float> prm = e->params<float>();
     prm.lg = p.lg;
-    return launch_lds<rollout_kernel<KS, RPL, PREC, MODE, LIT, LGE>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed,
+    return launch_lds<rollout_kernel<KS, RPL, PREC, MODE, LIT, LGE, GR>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale, c.seed,
                                                                       c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf, c.term_buf,
                                                                       c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term, c.next_trunc, p.rden_lds,
                                                                       p.epw, p.vec_ok, c.last_value, c.reward_sum, c.final_obs);
 }
 
-template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false>
+template <int KS, int RPL, int PREC, int MODE, int EPW, bool LIT = false, bool GR = false>
 static int roll_small(const pc_env* e, const RolloutPlan& p, const RolloutIO& c, hipStream_t st) {
     EnvParams<float> prm = e->params<float>();
     prm.lg = p.lg;
-    return launch_lds<rollout_small_kernel<KS, RPL, PREC, MODE, EPW, LIT>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale,
+    return launch_lds<rollout_small_kernel<KS, RPL, PREC, MODE, EPW, LIT, GR>>(e->device, p.blocks, p.lds, st, prm, c.image, c.A, c.T, c.reward_scale,
                                                                             c.seed, c.offset, c.offset_dev, c.obs_buf, c.act_buf, c.rew_buf, c.val_buf,
                                                                             c.term_buf, c.trunc_buf, c.logprob_buf, c.next_obs, c.next_term,
                                                                             c.next_trunc, p.rden_lds, p.vec_ok, c.last_value, c.reward_sum,
@@ -496,6 +497,29 @@ static auto roll_small_mode(int mode, bool epw16) {
     if constexpr (PREC != 0 && RPL <= 5)
         if (epw16) return roll_small<KS, RPL, PREC, 1, 16>;
     return mode ? roll_small<KS, RPL, PREC, 1, 32> : roll_small<KS, RPL, PREC, 0, 32>;
+}
+
+// pc_rollout_greedy's menu (F32 handles, fp16 x 2, Discrete(9), the table-driven modes): the greedy instance of the kernel plan_rollout
+// picks for the sampled call -- md = the kernel's MODE (1 / 2, at 16 rays also the chain layouts 3 / 4 / 5).  Not in a developer quick build.
+using RolloutLaunch = int (*)(const pc_env*, const RolloutPlan&, const RolloutIO&, hipStream_t);
+static int greedy_big(int KS, int rpl, int md, RolloutLaunch& out) {
+    if (KS == 5 && rpl == 6) PC_FULL(out = md == 2 ? roll_big<5, 6, 2, 2, false, 1, true> : roll_big<5, 6, 2, 1, false, 1, true>);
+    else if (KS == 6 && rpl == 9)
+        PC_FULL(out = md == 3 ? roll_big<6, 9, 2, 3, false, 1, true> : md == 5 ? roll_big<6, 9, 2, 5, false, 1, true>
+                    : md == 4 ? roll_big<6, 9, 2, 4, false, 1, true> : md == 2 ? roll_big<6, 9, 2, 2, false, 1, true>
+                              : roll_big<6, 9, 2, 1, false, 1, true>);
+    else if (KS == 10 && rpl == 17) PC_FULL(out = (roll_big<10, 17, 2, 1, false, 1, true>));
+    else return PC_ERR_UNSUPPORTED;
+    return PC_OK;
+}
+static int greedy_small(int KS, int rpl, bool epw16, bool rden, RolloutLaunch& out) {
+    if (KS == 5 && rpl == 3) PC_FULL(out = epw16 ? roll_small<5, 3, 2, 1, 16, false, true> : roll_small<5, 3, 2, 1, 32, false, true>);
+    else if (KS == 6 && rpl == 5)
+        PC_FULL(out = (epw16 && rden) ? roll_small<6, 5, 2, 2, 16, false, true> : epw16 ? roll_small<6, 5, 2, 1, 16, false, true>
+                                      : roll_small<6, 5, 2, 1, 32, false, true>);
+    else if (KS == 10 && rpl == 9) PC_FULL(out = (roll_small<10, 9, 2, 1, 32, false, true>));
+    else return PC_ERR_UNSUPPORTED;
+    return PC_OK;
 }
 
 extern "C" {
@@ -1124,7 +1148,7 @@ static int policy_pack_impl(int device, int prec, int D, int H, int A, const flo
 
 static int policy_act_impl(int device, int prec, int split_mode, const float* obs, int64_t N, int D, int H, int A, const float* image, uint64_t seed,
                            uint64_t offset, const uint64_t* offset_dev, int64_t* action, float* action_f32, float* logprob, float* value,
-                           float* logits_out, void* stream) {
+                           float* logits_out, void* stream, bool greedy = false) {
     if (!obs || !image || !action || !logprob || !value || N < 1) return PC_ERR_INVALID_ARG;
     if (!mlp_shape_ok(D, H, A)) return PC_ERR_UNSUPPORTED;  // the caller falls back to its own GEMMs
     if (!valid_device(device)) return PC_ERR_NO_DEVICE;
@@ -1141,7 +1165,8 @@ static int policy_act_impl(int device, int prec, int split_mode, const float* ob
     const int blocks = (int)(chunks < cus ? chunks : cus);  // one ~100-KB-LDS workgroup per CU, persistent over env chunks
     hipStream_t st = (hipStream_t)stream;
     int (*run)(bool, int, int, size_t, hipStream_t, const PolicyArgs&) = nullptr;
-    if (prec == 2 && KS != 5) run = KS == 6 ? run_policy<6, 2> : run_policy<10, 2>;     // (what a quick build keeps)
+    if (greedy) PC_FULL(run = prec == 2 ? policy_run_for<2, true>(KS) : prec == 1 ? policy_run_for<1, true>(KS) : policy_run_for<0, true>(KS));
+    else if (prec == 2 && KS != 5) run = KS == 6 ? run_policy<6, 2> : run_policy<10, 2>;     // (what a quick build keeps)
     else PC_FULL(run = prec == 2 ? run_policy<5, 2> : prec == 1 ? policy_run_for<1>(KS) : policy_run_for<0>(KS));
     return run(split, device, blocks, lds, st, {obs, N, D, A, image, seed, offset, offset_dev, action, action_f32, logprob, value, logits_out});
 }
@@ -1167,6 +1192,14 @@ int pc_policy_act(const pc_policy* p, const float* obs, int64_t N, const float* 
     if (!p) return PC_ERR_INVALID_ARG;
     return policy_act_impl(p->device, p->precision, p->split, obs, N, p->D, p->H, p->A, image, seed, offset, offset_dev, action, action_f32,
                            logprob, value, logits_out, stream);
+}
+
+int pc_policy_act_greedy(const pc_policy* p, const float* obs, int64_t N, const float* image, int64_t* action, float* action_f32,
+                         float* logprob, float* value, float* logits_out, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!p) return PC_ERR_INVALID_ARG;
+    return policy_act_impl(p->device, p->precision, p->split, obs, N, p->D, p->H, p->A, image, 0, 0, nullptr, action, action_f32, logprob, value,
+                           logits_out, stream, true);
 }
 
 int pc_ppo_gather(int device, const int64_t* idx, int B, int D, const float* obs, const float* act, const float* logprob,
@@ -1285,9 +1318,12 @@ int pc_clip_adam_advanced(int device, float* param, const float* grad, float* ex
 // pc_rollout's choice for this handle and call: PC_OK with `p` filled, or PC_ERR_UNSUPPORTED (the caller then runs the per-step kernels,
 // which fill the same buffers bit for bit).  The rules run in order of preference.  F32 and F64 handles share the two-track and the
 // 16-envs-per-wave forms (LIT: an F64 handle, whose env step is the literal form); every other rule belongs to one dtype.
-static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPlan& p) {
+// `greedy` (pc_rollout_greedy): the same form as for the sampled call on this handle -- kernel id, envs per workgroup, blocks, LDS bytes, 1/den
+// table -- where that form is on the greedy menu (greedy_big / greedy_small and the 16-envs-per-wave form), else PC_ERR_UNSUPPORTED.
+static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, bool greedy, RolloutPlan& p) {
     const bool lit = e->dtype == PC_DTYPE_F64;
     if (lit ? A != 9 : (A < 1 || A > 15)) return PC_ERR_UNSUPPORTED;
+    if (greedy && (lit || prec != 2 || A != 9)) return PC_ERR_UNSUPPORTED;
     const RolloutOpts& o = e->opt;
     const TrackFacts& f = e->facts;
     const bool all_nv28 = o.nv28 != 0 && f.nv28, all_loops = o.nv28 != 0 && f.loops;
@@ -1296,6 +1332,7 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
     // kernel K9d -- the fast and literal forms stage ONE track's tables per workgroup, and the small form's sweep parts meet across
     // workgroup barriers that a per-wave loop cannot contain
     const bool interleaved = e->track_id && !e->track_blocks32;
+    if (greedy && interleaved) return PC_ERR_UNSUPPORTED;     // (the two-track modes 6 / 7 and the generic mode: not on the greedy menu)
     const int KS = policy_ks(e->D);
     const int img = prec ? polx_image_dwords(prec, pol_ng(KS)) : pol_image_padded(KS);
     // 12 / 16 / 32 nominal rays: 12 / 17 / 33 actual, D = 18 / 23 / 39 (KS = 5 / 6 / 10), 6 / 9 / 17 ray slots on two lanes per env
@@ -1362,7 +1399,8 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
         if (want_m && rays16 && prec == 2 && A == 9 && e->D >= 17 && e->D <= 40 && f.max_G <= TAB_MAX_GATES && f.max_nV <= FT_VTX_MAX && o.fast &&
             o.rden != 0 && (all_nv28 || all_loops) && (!e->track_id || e->track_block >= 128) && lds_m <= 160 * 1024 &&
             (!lit || (f.tabs && !e->f64_offgrid && (!e->track_id || e->track_block >= epw) && lds_sel <= 160 * 1024))) {
-            if (lit) { if (all_nv28) PC_DEV(8, p.launch = roll_big<6, 5, 2, 3, true, 2>); else PC_FULL(p.launch = roll_big<6, 5, 2, 5, true, 2>); }
+            if (greedy) PC_FULL(p.launch = all_nv28 ? roll_big<6, 5, 2, 3, false, 2, true> : roll_big<6, 5, 2, 5, false, 2, true>);
+            else if (lit) { if (all_nv28) PC_DEV(8, p.launch = roll_big<6, 5, 2, 3, true, 2>); else PC_FULL(p.launch = roll_big<6, 5, 2, 5, true, 2>); }
             else { if (all_nv28) PC_DEV(7, p.launch = roll_big<6, 5, 2, 3, false, 2>); else PC_FULL(p.launch = roll_big<6, 5, 2, 5, false, 2>); }
             p.blocks = (int)((e->N + 127) / 128);
             p.lds = lds_m;
@@ -1462,9 +1500,15 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
         p.rden_lds = 0;
     p.lds += (size_t)p.rden_lds * sizeof(float);
     const int mode = (fast || fast_small) ? (p.rden_lds ? 2 : 1) : 0;
+    if (greedy && !mode) return PC_ERR_UNSUPPORTED;           // (the generic mode)
     if (!small) {
         const int rpl = (e->R + 1) / 2;       // 2 lanes per env
-        if (KS == 5 && rpl == 6) {           // 12 rays, D = 18
+        if (greedy) {                        // the instance the rules below pick, in its greedy form
+            const bool r16 = KS == 6 && rpl == 9;
+            const int md = (r16 && mode == 2 && all_nv28) ? 3 : (r16 && mode == 2 && all_loops) ? 5 : (r16 && mode == 1 && all_nv28) ? 4 : mode;
+            const int rc = greedy_big(KS, rpl, md, p.launch);
+            if (rc != PC_OK) return rc;
+        } else if (KS == 5 && rpl == 6) {    // 12 rays, D = 18
             PC_FULL(p.launch = prec == 2 ? roll_big_mode<5, 6, 2>(mode) : prec ? roll_big_mode<5, 6, 1>(mode) : roll_big_mode<5, 6, 0>(mode));
         } else if (KS == 6 && rpl == 9) {    // 16 -> 17 rays, D = 23; fp16 x 2: the chain-of-28 and chain-packed kernels
             if (prec == 2 && mode == 2 && all_nv28) PC_DEV(0, p.launch = (roll_big<6, 9, 2, 3>));
@@ -1487,7 +1531,10 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
     if (epw_small == 16 && !(fast_small && prec != 0 && e->R <= 17)) return PC_ERR_UNSUPPORTED;
     const bool epw16 = mode && epw_small == 16;
     const int rpl = (e->R + 3) / 4;           // 4 lanes per env (x 4 sweep parts)
-    if (KS == 5 && rpl == 3) {               // 12 rays
+    if (greedy) {                            // the instance the rules below pick, in its greedy form
+        const int rc = greedy_small(KS, rpl, epw16, p.rden_lds != 0, p.launch);
+        if (rc != PC_OK) return rc;
+    } else if (KS == 5 && rpl == 3) {        // 12 rays
         PC_FULL(p.launch = prec == 2 ? roll_small_mode<5, 3, 2>(mode, epw16) : prec ? roll_small_mode<5, 3, 1>(mode, epw16) : roll_small_mode<5, 3, 0>(mode, epw16));
     } else if (KS == 6 && rpl == 5) {        // 16 -> 17 rays (configs[1]'s kernel: with the 1/den table in LDS the env step is compiled for it)
         if (prec == 2 && epw16 && p.rden_lds) PC_DEV(1, p.launch = (roll_small<6, 5, 2, 2, 16>));
@@ -1505,7 +1552,7 @@ static int plan_rollout(const pc_env* e, int prec, int A, int vec_ok, RolloutPla
 static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
                        const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
                        float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
-                       float* reward_sum, float* final_obs, hipStream_t stream);
+                       float* reward_sum, float* final_obs, hipStream_t stream, bool greedy = false);
 
 int pc_rollout(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
                const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
@@ -1526,11 +1573,20 @@ int pc_rollout_final_obs(pc_env* e, const pc_policy* p, const float* image, int6
                        next_obs, next_term, next_trunc, last_value, reward_sum, final_obs, (hipStream_t)stream);
 }
 
-// pc_rollout / pc_rollout_final_obs: one dispatch (plan_rollout), one launch
+int pc_rollout_greedy(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, float* obs_buf, float* act_buf,
+                      float* rew_buf, float* val_buf, float* term_buf, float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term,
+                      float* next_trunc, float* last_value, float* reward_sum, float* final_obs, int64_t slots, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (final_obs && (T < 1 || slots < (T + PC_TIME_LIMIT - 1) / PC_TIME_LIMIT)) return PC_ERR_INVALID_ARG;
+    return rollout_run(e, p, image, T, reward_scale, 0, 0, nullptr, obs_buf, act_buf, rew_buf, val_buf, term_buf, trunc_buf, logprob_buf, next_obs,
+                       next_term, next_trunc, last_value, reward_sum, final_obs, (hipStream_t)stream, true);
+}
+
+// pc_rollout / pc_rollout_final_obs / pc_rollout_greedy: one dispatch (plan_rollout), one launch
 static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_t T, double reward_scale, uint64_t seed, uint64_t offset,
                        const uint64_t* offset_dev, float* obs_buf, float* act_buf, float* rew_buf, float* val_buf, float* term_buf,
                        float* trunc_buf, float* logprob_buf, float* next_obs, float* next_term, float* next_trunc, float* last_value,
-                       float* reward_sum, float* final_obs, hipStream_t stream) {
+                       float* reward_sum, float* final_obs, hipStream_t stream, bool greedy) {
     if (!e || !p) return PC_ERR_INVALID_ARG;
     if (p->D != e->D || p->device != e->device) return PC_ERR_INVALID_ARG;     // the policy was built for another observation width / device
     if (!image || !obs_buf || !act_buf || !rew_buf || !val_buf || !term_buf || !trunc_buf || !logprob_buf || !next_obs || !next_term || !next_trunc ||
@@ -1539,7 +1595,7 @@ static int rollout_run(pc_env* e, const pc_policy* p, const float* image, int64_
     // 16-byte stores of the waves' 32-row blocks: the rows' offsets inside the buffers AND the buffers themselves are aligned
     const int vec_ok = ((e->N * e->D) % 4 == 0 && (((uintptr_t)obs_buf | (uintptr_t)next_obs) & 15) == 0) ? 1 : 0;
     RolloutPlan plan;
-    int rc = plan_rollout(e, policy_prec(p->precision, e->D, p->A), p->A, vec_ok, plan);
+    int rc = plan_rollout(e, policy_prec(p->precision, e->D, p->A), p->A, vec_ok, greedy, plan);
     if (rc != PC_OK) return rc;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;

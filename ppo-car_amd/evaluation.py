@@ -12,10 +12,13 @@ pc_first_episodes.  CarEnv truncates at time >= 1000 (car_env.py:745-750), so af
 first episode: no early stop, no host synchronisation.  The draw of step t comes from the stream (seed, offset = index * 1000 + t,
 idx = env), so run(index) is reproducible and two indices never share a draw.
   sampled, a shape pc_rollout takes : one pc_rollout per window (Buffer layout)                             last_path == "mega"
-  rollout_kernel="steps", greedy=True, or a shape pc_rollout refuses: per step pc_policy_act (+ pc_greedy on its logits when greedy),
-                                      then pc_env_step into step-layout rows                                last_path == "steps"
+  greedy=True, rollout_kernel="mega", a shape pc_rollout_greedy takes: one pc_rollout_greedy per window     last_path == "mega"
+  rollout_kernel="steps", greedy=True with "auto", or a shape the persistent kernel refuses: per step pc_policy_act (greedy:
+                                      pc_policy_act_greedy), then pc_env_step into step-layout rows         last_path == "steps"
   an agent outside the fused kernel's menu: agent.actor(obs) + pc_sample / pc_greedy                        last_path == "steps"
-pc_rollout == T x (pc_policy_act; pc_env_step) bit for bit, so the two sampled paths leave the same state bits."""
+pc_rollout == T x (pc_policy_act; pc_env_step) and pc_rollout_greedy == T x (pc_policy_act_greedy; pc_env_step) bit for bit, so the two
+paths of either kind leave the same state bits.  (Making "mega" what "auto" means for greedy evaluations too is a one-line change in
+__init__ below, once pc_rollout_greedy has run in anger.)"""
 import math
 import sys
 
@@ -91,14 +94,13 @@ class Evaluator:
         self.state = new_state(N, self.device)
         self._state0 = self.state.clone()
         self._fused = bool(agent._std_mlp()) and agent.policy_form() is not None
-        self._mega = self._fused and not self.greedy and rollout_kernel != "steps"
+        self._mega = self._fused and (rollout_kernel == "mega" if self.greedy else rollout_kernel != "steps")
         self._image = self._image_handle = None
         self._range = torch.zeros(1, dtype=torch.int32, device=self.device)
         # rows of one window (both layouts), the observation / flags the next step starts from, and the per-step outputs
         self._rew, self._term, self._trunc = new(C, N), new(C, N), new(C, N)
         self._next_obs, self._next_term, self._next_trunc = new(N, D), new(N), new(N)
         self._act, self._logprob, self._val = new(N, dtype=torch.int64), new(N), new(N)
-        self._logits = new(N, A) if self.greedy else None
         self._mega_rows = None
         if self._mega:
             self._alloc_mega()
@@ -134,18 +136,22 @@ class Evaluator:
               "pc_first_episodes")
 
     def _window_mega(self, h, T, offset):
-        """pc_rollout over T steps: rows in the Buffer layout.  False = the shape is outside the persistent kernel's menu."""
+        """pc_rollout (greedy: pc_rollout_greedy) over T steps: rows in the Buffer layout.  False = the shape is outside the persistent
+        kernel's menu."""
         m = self._mega_rows
         m["obs"][0].copy_(self._next_obs)
         self._term[0].copy_(self._next_term)
         self._trunc[0].copy_(self._next_trunc)
-        rc = lib.pc_rollout(self.envs._h, h, self._image.data_ptr(), T, self.reward_scaling, self.seed, offset, None, m["obs"].data_ptr(),
-                            m["act"].data_ptr(), self._rew.data_ptr(), m["val"].data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(),
-                            m["logprob"].data_ptr(), self._next_obs.data_ptr(), self._next_term.data_ptr(), self._next_trunc.data_ptr(),
-                            None, None, self._stream())
+        rows = (m["obs"].data_ptr(), m["act"].data_ptr(), self._rew.data_ptr(), m["val"].data_ptr(), self._term.data_ptr(),
+                self._trunc.data_ptr(), m["logprob"].data_ptr(), self._next_obs.data_ptr(), self._next_term.data_ptr(),
+                self._next_trunc.data_ptr(), None, None)
+        if self.greedy:
+            rc = lib.pc_rollout_greedy(self.envs._h, h, self._image.data_ptr(), T, self.reward_scaling, *rows, None, 0, self._stream())
+        else:
+            rc = lib.pc_rollout(self.envs._h, h, self._image.data_ptr(), T, self.reward_scaling, self.seed, offset, None, *rows, self._stream())
         if rc == _capi.PC_ERR_UNSUPPORTED:
             return False
-        check(rc, "pc_rollout")
+        check(rc, "pc_rollout_greedy" if self.greedy else "pc_rollout")
         self._scan(T, PC_EPISODE_BUFFER)
         return True
 
@@ -153,19 +159,20 @@ class Evaluator:
         """T x (policy step; env step): rows in the step layout, the observation stepped in place."""
         N, di, st = self.num_envs, self.device.index, self._stream()
         obs, act = self._next_obs, self._act
-        logits = self._logits.data_ptr() if self.greedy else None
         for t in range(T):
-            if h is not None:
+            if h is not None and self.greedy:       # the argmax inside the policy step: two launches per step, no logits buffer
+                check(lib.pc_policy_act_greedy(h, obs.data_ptr(), N, self._image.data_ptr(), act.data_ptr(), None, self._logprob.data_ptr(),
+                                               self._val.data_ptr(), None, st), "pc_policy_act_greedy")
+            elif h is not None:
                 check(lib.pc_policy_act(h, obs.data_ptr(), N, self._image.data_ptr(), self.seed, offset + t, None, act.data_ptr(), None,
-                                        self._logprob.data_ptr(), self._val.data_ptr(), logits, st), "pc_policy_act")
+                                        self._logprob.data_ptr(), self._val.data_ptr(), None, st), "pc_policy_act")
             else:           # outside the fused kernel's menu: torch's GEMMs in front of the draw
                 lg = self.agent.actor(obs).contiguous()
-                logits = lg.data_ptr()
-                if not self.greedy:
-                    check(lib.pc_sample(di, logits, N, lg.shape[1], self.seed, offset + t, act.data_ptr(), self._logprob.data_ptr(), None,
-                                        st), "pc_sample")
-            if self.greedy:
-                check(lib.pc_greedy(di, logits, N, self.envs.act_dim, act.data_ptr(), None, None, st), "pc_greedy")
+                if self.greedy:
+                    check(lib.pc_greedy(di, lg.data_ptr(), N, self.envs.act_dim, act.data_ptr(), None, None, st), "pc_greedy")
+                else:
+                    check(lib.pc_sample(di, lg.data_ptr(), N, lg.shape[1], self.seed, offset + t, act.data_ptr(), self._logprob.data_ptr(),
+                                        None, st), "pc_sample")
             self.envs.step(act, out=(obs, self._rew[t], self._term[t], self._trunc[t]))
         self._scan(T, PC_EPISODE_STEPS)
 

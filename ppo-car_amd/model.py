@@ -164,14 +164,18 @@ class Agent(nn.Module):
 
     @torch.no_grad()
     def act(self, x, out_action=None, out_logprob=None, out_value=None, out_action_f32=None, out_logits=None, fused=True,
-            repack=True, offset_dev=None, offset=None):
+            repack=True, offset_dev=None, offset=None, greedy=False):
         """Rollout-time variant of get_action_and_value(x): same distribution, no autograd.
         fused=True: ONE HIP kernel (pc_policy_act) -- both MLPs on the fp32 matrix cores, the categorical
         draw, log_prob and the value; falls back to the two-kernel form when the shape is outside its menu.
         repack=False reuses the weight image of the last pack_policy() (the rollout packs once).
         fused=False: torch GEMMs for the MLPs + the sampling-tail kernel (pc_sample).
         Counter-based Philox stream keyed by (rng_seed, offset [+ *offset_dev]); offset defaults to a per-agent
-        call counter.  Returns action int64 [N], logprob [N], value [N] (written into the out_* tensors when given)."""
+        call counter.  Returns action int64 [N], logprob [N], value [N] (written into the out_* tensors when given).
+        greedy=True: the first argmax of the logits in place of the draw (torch.argmax's tie rule) -- on a fused handle ONE kernel
+        (pc_policy_act_greedy), else torch's GEMMs + pc_greedy.  No random number is used: the call counter does not advance."""
+        if greedy:
+            offset = 0 if offset is None else offset
         if offset is None:
             offset = self._rng_offset
             self._rng_offset += 1
@@ -188,16 +192,23 @@ class Agent(nn.Module):
             ok = h is not None and (self.pack_policy() if (repack or stale) else True)
             if ok:
                 value = out_value if out_value is not None else torch.empty(N, dtype=torch.float32, device=dev)
+                if greedy:
+                    check(lib.pc_policy_act_greedy(h, x.data_ptr(), N, self._image.data_ptr(), action.data_ptr(), ptr(out_action_f32),
+                                                   logprob.data_ptr(), value.data_ptr(), ptr(out_logits), stream), "pc_policy_act_greedy")
+                    return action, logprob, value
                 check(lib.pc_policy_act(h, x.data_ptr(), N, self._image.data_ptr(), int(self.rng_seed), int(offset), ptr(offset_dev),
                                           action.data_ptr(), ptr(out_action_f32), logprob.data_ptr(), value.data_ptr(), ptr(out_logits),
                                           stream), "pc_policy_act")
                 return action, logprob, value
-        if offset_dev is not None:
+        if offset_dev is not None and not greedy:
             raise NotImplementedError("a device-side RNG offset needs the fused policy kernel")
         logits = self.actor(x).contiguous()
         A = logits.shape[1]
-        check(lib.pc_sample(di, logits.data_ptr(), N, A, int(self.rng_seed), int(offset), action.data_ptr(),
-                            logprob.data_ptr(), None, stream), "pc_sample")
+        if greedy:
+            check(lib.pc_greedy(di, logits.data_ptr(), N, A, action.data_ptr(), None, logprob.data_ptr(), stream), "pc_greedy")
+        else:
+            check(lib.pc_sample(di, logits.data_ptr(), N, A, int(self.rng_seed), int(offset), action.data_ptr(),
+                                logprob.data_ptr(), None, stream), "pc_sample")
         value = self.critic(x).view(-1)
         if out_value is not None:
             out_value.copy_(value)

@@ -120,7 +120,9 @@ class PPOConfig:
                                            # env handle, weight image and random stream; training computes the same bits with it on or off).
                                            # Rank 0 only.  0 = off: not one launch is added to an epoch
     eval_envs: int = 1024                  # envs (= episodes) per evaluation
-    eval_greedy: bool = False              # argmax actions (pc_greedy) instead of draws
+    eval_greedy: bool = False              # argmax actions instead of draws
+    eval_rollout_kernel: str = "auto"      # how evaluations step: "mega" = persistent launches (greedy: pc_rollout_greedy), "steps" = the per-step
+                                           # kernels, "auto" = mega for sampled evaluations, steps for greedy ones; rollout_kernel = "steps" forces "steps"
     eval_track: str | list | None = None   # the track(s) evaluated on; None = `track` (with track_interleave); another file = a held-out track
 
     def __post_init__(self):
@@ -128,6 +130,8 @@ class PPOConfig:
             raise ValueError(f"PPOConfig.eval_every must be >= 0 (0 = off), not {self.eval_every!r}")
         if self.eval_envs < 1:
             raise ValueError(f"PPOConfig.eval_envs must be >= 1, not {self.eval_envs!r}")
+        if self.eval_rollout_kernel not in ("auto", "mega", "steps"):
+            raise ValueError(f"PPOConfig.eval_rollout_kernel must be 'auto', 'mega' or 'steps', not {self.eval_rollout_kernel!r}")
         if self.truncation_bootstrap not in ("reference", "final_obs"):
             raise ValueError(f"PPOConfig.truncation_bootstrap must be 'reference' or 'final_obs', not {self.truncation_bootstrap!r}")
         if self.target_kl is not None:
@@ -902,7 +906,7 @@ class Trainer:
                                        device=self.device, dtype=cfg.env_dtype,
                                        track_id=mixed_track_ids(ev_track, cfg.eval_envs, cfg.track_interleave),
                                        greedy=cfg.eval_greedy, seed=cfg.seed * 1000003 + 0x9E3779B9,
-                                       rollout_kernel="steps" if cfg.rollout_kernel == "steps" else "auto")
+                                       rollout_kernel="steps" if cfg.rollout_kernel == "steps" else cfg.eval_rollout_kernel)
 
     # ---- train.py:173-195 ---------------------------------------------------------------------------
     @torch.no_grad()

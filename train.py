@@ -68,6 +68,9 @@ def parse_args(argv=None):
                    "--eval-envs fresh envs and log eval/* (return, length, gates, laps, crash rate, lap times in steps); 0 = off")
     p.add_argument("--eval-envs", type=int, default=1024, help="envs (= episodes) per evaluation")
     p.add_argument("--eval-greedy", action="store_true", help="evaluate with argmax actions instead of draws")
+    p.add_argument("--eval-rollout-kernel", choices=("auto", "mega", "steps"), default="auto",
+                   help="how evaluations step: 'mega' = persistent launches (with --eval-greedy: pc_rollout_greedy), 'steps' = the per-step "
+                   "kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
     p.add_argument("--eval-track", default=None, help="track JSON to evaluate on (default: --track; another file = a held-out track)")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
@@ -114,7 +117,7 @@ def main(argv=None):
                     episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap,
                     update_diagnostics=args.update_diagnostics, target_kl=args.target_kl,
                     large_minibatch=args.large_minibatch, eval_every=args.eval_every, eval_envs=args.eval_envs,
-                    eval_greedy=args.eval_greedy, eval_track=args.eval_track)
+                    eval_greedy=args.eval_greedy, eval_track=args.eval_track, eval_rollout_kernel=args.eval_rollout_kernel)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
