@@ -8,6 +8,8 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
     python evaluate.py --checkpoint ... --envs 4096 [--greedy]       # batched: the first episodes of 4096 envs (ppo_car_amd.Evaluator),
                                                                      # JSON with the eval/* scalars (lap times in steps) and the path taken
     python evaluate.py --checkpoint ... --envs 4096 --greedy --rollout-kernel mega     # ... the greedy windows as persistent launches
+    python evaluate.py --checkpoint ... --envs 4096 --maps out/eval                    # ... plus telemetry maps of those first episodes:
+                                                                     # out/eval.npz and a PNG per plane (visits, mean speed, crashes)
 """
 import argparse
 import json
@@ -30,6 +32,8 @@ def parse_args(argv=None):
     ap.add_argument("--rollout-kernel", choices=("auto", "mega", "steps"), default="auto",
                     help="--envs: how the Evaluator steps -- 'mega' = persistent launches (pc_rollout; with --greedy pc_rollout_greedy), 'steps' = "
                     "the per-step kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
+    ap.add_argument("--maps", default=None, metavar="PREFIX", help="--envs: write telemetry maps of the first episodes (ppo_car_amd.TrackMaps: "
+                    "visits, mean speed and crashes per cell) to PREFIX.npz and PREFIX_<track>_<plane>.png")
     return ap.parse_args(argv)
 
 
@@ -92,10 +96,12 @@ def batched(pc, args):
     agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
     agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     ev = pc.Evaluator(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda", greedy=args.greedy,
-                      seed=args.seed, rollout_kernel=args.rollout_kernel)
+                      seed=args.seed, rollout_kernel=args.rollout_kernel, track_maps=args.maps is not None)
     try:
         out = ev.evaluate()
         out["path"] = ev.last_path
+        if args.maps is not None:
+            out["maps"] = ev.maps.save(args.maps, ev.envs._tracks)
     finally:
         ev.close()
     print(json.dumps(out))

@@ -269,6 +269,42 @@ int pc_first_episodes(int device, const float* rew, const float* term, const flo
                       const float* last_trunc, int64_t T, int64_t N, int layout, double reward_scale, double* state, void* stream);
 int pc_greedy(int device, const float* logits, int64_t N, int A, int64_t* actions, float* action_f32, float* logprob, void* stream);
 
+/* ---- track telemetry maps (opt-in: the entry points above are untouched): WHERE on the track the cars drive, how fast, and where
+ * they crash.  One streaming pass over observation rows that are already on the device (entries 0-3 of an observation are x / 1280,
+ * y / 720, vx / max_speed, vy / max_speed, car_env.py:578-581), reduced to integer counters per cell of cell_px x cell_px pixels.
+ * pc_track_maps: obs [T][N][D] float32 -- in both layouts row t is the observation the policy acted on at step t, i.e. the car's pose
+ *   BEFORE step t; only entries 0-3 of a row are read.  term / trunc / last_* / layout exactly as pc_first_episodes takes them
+ *   (PC_EPISODE_BUFFER: step t's flags in row t + 1, step T - 1's in last_*, row 0 never read; PC_EPISODE_STEPS: flags[t] belong to
+ *   step t, last_* may be NULL).  track_id [N] uint8 (device), NULL = every env on track 0.
+ *   maps [n_tracks][PC_MAP_PLANES][GH][GW] int64 (device), GW = 1280 / cell_px, GH = 720 / cell_px: ACCUMULATED, the caller zeroes it
+ *   once.  cell_px is one of 4, 5, 8, 10, 16, 20, 40, 80 (the divisors of 80 from 4 upward).
+ *   first_state: NULL = every sample counts; or pc_first_episodes' [PC_FIRST_ROWS][N] state as it stands BEFORE that window's scan
+ *   (read-only, only row 4 is read; call pc_track_maps before pc_first_episodes for each window): a sample then counts only if env
+ *   n's status on entry is PC_FIRST_RUNNING and no earlier step of this window had env n's term or trunc flag set -- the closing step
+ *   itself counts, everything after it does not: pc_first_episodes' own rule, so the maps cover exactly the first episodes.
+ *   Per counted sample (t, n):
+ *     cell   cx = clamp((int)floorf(o0 * (float)GW), 0, GW - 1), cy = clamp((int)floorf(o1 * (float)GH), 0, GH - 1), each product ONE
+ *            float32 multiply.  A sample whose o0 or o1 is not finite, or whose track_id[n] >= n_tracks, is skipped entirely.
+ *     speed  q = (int64)rint(sqrt((double)o2 * o2 + (double)o3 * o3) * PC_MAP_SPEED_UNIT): both products exact in float64, one
+ *            rounding in the sum, a correctly rounded sqrt -- a numpy float64 expression gives the same integer.  (A speed that is
+ *            not finite, or above 9e18 units, counts as q = 0; the env's own rows have |o2|, |o3| <= 1.)
+ *     VISITS += 1, SPEED += q; CRASHES += 1 when step t's term flag is non-zero (a truncation is not a crash).
+ *   The crash cell is the cell of the LAST OBSERVATION BEFORE the hit: the pose the failing action was chosen in, not the point of
+ *   impact -- the car moves at most max_speed = 10 px per axis in that step, so the impact lies in that cell or next to it.
+ *   All accumulation is integer (64-bit adds, no floating-point atomics): the maps are bit-identical whatever the launch geometry
+ *   or the order in which samples arrive.
+ *   Checked before any device call, in this order: NULL obs / term / trunc / maps, T < 1, N < 1, D < 4, a layout other than the two,
+ *   NULL last_* in the Buffer layout, n_tracks < 1 or > 256, a cell_px off the list: PC_ERR_INVALID_ARG; then device < 0 or unknown:
+ *   PC_ERR_NO_DEVICE.  Never synchronises. */
+#define PC_MAP_VISITS 0      /* samples whose car was in the cell */
+#define PC_MAP_SPEED 1       /* sum over those samples of q = speed in units of max_speed / PC_MAP_SPEED_UNIT */
+#define PC_MAP_CRASHES 2     /* samples whose step terminated (a wall hit); a truncation is not a crash */
+#define PC_MAP_PLANES 3
+#define PC_MAP_SPEED_UNIT 1024
+int pc_track_maps(int device, const float* obs, int64_t D, const float* term, const float* trunc, const float* last_term,
+                  const float* last_trunc, int64_t T, int64_t N, int layout, const uint8_t* track_id, int n_tracks, int cell_px,
+                  const double* first_state, int64_t* maps, void* stream);
+
 /* ---- the whole of Agent.get_action_and_value(x) as the rollout calls it (model.py:34-41, train.py:181):
  * both 1-hidden-layer MLPs (actor D->H->A, critic D->H->1, ReLU), the categorical draw, log_prob and the
  * value, in one launch on the matrix cores.  A policy step's configuration is a HANDLE: shape (D, H, A), arithmetic form of the

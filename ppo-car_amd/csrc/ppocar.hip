@@ -1,5 +1,5 @@
 // ppocar.hip -- HIP kernels (gfx950 / CDNA4) and the C-ABI of libppocar.so.  ONE translation unit: the kernels live in
-// kernels/*.hpp (env_math, env_step, gae_sample, evaluation, policy, rollout, update), included below in dependency order; this file
+// kernels/*.hpp (env_math, env_step, gae_sample, evaluation, track_maps, policy, rollout, update), included below in dependency order; this file
 // holds the host side (handles, launch configuration, the extern "C" entry points of include/ppocar.h).  The track loader
 // (track_json.cpp) and the compiler of the tracks into the env kernels' tables (track_tables.cpp) are host-only units of their own.
 //
@@ -24,6 +24,7 @@
 //   K13 xchg_allreduce_kernel          the per-minibatch gradient all-reduce as a one-shot exchange over peer-mapped buffers (pc_xchg_*)
 //   K14 first_episodes_kernel<STEPS>   the forward scan of the batched evaluation: each env's first episode and its lap times (pc_first_episodes)
 //   K15 greedy_kernel                  argmax action + its log_prob, the deterministic sibling of K4 (pc_greedy)
+//   K16 track_maps_kernel<STEPS, FIRST>   the observation rows of a rollout reduced to per-cell visit, speed and crash counters (pc_track_maps)
 //
 // Work decomposition of K1: an env is owned by G = 2^lg consecutive lanes of one
 // wavefront ("lanes per env", chosen on the host from n_envs so the chip is filled); lane g of the
@@ -77,6 +78,7 @@
 #include "kernels/env_step.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
+#include "kernels/track_maps.hpp"
 #include "kernels/policy.hpp"
 #include "kernels/rollout.hpp"
 #include "kernels/env_steps.hpp"
@@ -1024,6 +1026,36 @@ static int device_cus(int device, int* out) {
         n_cu[device].store(c, std::memory_order_relaxed);
     }
     *out = c;
+    return PC_OK;
+}
+
+int pc_track_maps(int device, const float* obs, int64_t D, const float* term, const float* trunc, const float* last_term,
+                  const float* last_trunc, int64_t T, int64_t N, int layout, const uint8_t* track_id, int n_tracks, int cell_px,
+                  const double* first_state, int64_t* maps, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!obs || !term || !trunc || !maps || T < 1 || N < 1 || D < 4) return PC_ERR_INVALID_ARG;
+    if (layout != PC_EPISODE_BUFFER && layout != PC_EPISODE_STEPS) return PC_ERR_INVALID_ARG;
+    if (layout == PC_EPISODE_BUFFER && (!last_term || !last_trunc)) return PC_ERR_INVALID_ARG;
+    if (n_tracks < 1 || n_tracks > 256) return PC_ERR_INVALID_ARG;
+    if (cell_px < 4 || cell_px > 80 || 80 % cell_px != 0) return PC_ERR_INVALID_ARG;     // 4, 5, 8, 10, 16, 20, 40, 80
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    int cus = 256;
+    if (const int rc = device_cus(device, &cus); rc != PC_OK) return rc;
+    // one lane per env; without first_state the rows are cut so that about two workgroups per compute unit walk them side by side
+    // (fewer, longer walks = fewer flushes of the LDS planes); with it every env's walk is the whole window
+    const int64_t gx = (N + 1023) / 1024;
+    int64_t gy = 1;
+    if (!first_state) gy = std::clamp<int64_t>((2 * (int64_t)cus + gx - 1) / gx, 1, T);
+    const int64_t rows = (T + gy - 1) / gy;
+    gy = (T + rows - 1) / rows;
+    const bool steps = layout == PC_EPISODE_STEPS;
+    const auto k = first_state ? (steps ? track_maps_kernel<true, true> : track_maps_kernel<false, true>)
+                               : (steps ? track_maps_kernel<true, false> : track_maps_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)gy), dim3(1024), 0, (hipStream_t)stream, obs, D, term, trunc, last_term, last_trunc,
+                       T, N, rows, track_id, n_tracks, 1280 / cell_px, 720 / cell_px, first_state, (unsigned long long*)maps);
+    HIPCHK(hipGetLastError());
     return PC_OK;
 }
 

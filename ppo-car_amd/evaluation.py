@@ -18,7 +18,13 @@ idx = env), so run(index) is reproducible and two indices never share a draw.
   an agent outside the fused kernel's menu: agent.actor(obs) + pc_sample / pc_greedy                        last_path == "steps"
 pc_rollout == T x (pc_policy_act; pc_env_step) and pc_rollout_greedy == T x (pc_policy_act_greedy; pc_env_step) bit for bit, so the two
 paths of either kind leave the same state bits.  (Making "mega" what "auto" means for greedy evaluations too is a one-line change in
-__init__ below, once pc_rollout_greedy has run in anger.)"""
+__init__ below, once pc_rollout_greedy has run in anger.)
+
+track_maps=True: the evaluator owns a TrackMaps (track_maps.py), one plane set per track of its handle, cleared by run() and updated
+in front of every window's pc_first_episodes with the state as it stands there -- the maps cover exactly the first episodes.  The
+persistent path has the observation rows already; the per-step path then keeps the window's rows (step t reads row t and writes row
+t + 1, the window's last step writes _next_obs) instead of stepping one row in place: the same launches on other addresses, the same
+state bits.  Off: not one launch or buffer is added."""
 import math
 import sys
 
@@ -28,6 +34,7 @@ from . import _capi
 from ._capi import PC_EPISODE_BUFFER, PC_EPISODE_STEPS, PC_FIRST_ROWS, PC_TIME_LIMIT, check, lib
 from .env import VecCarEnv
 from .model import PolicyRangeError
+from .track_maps import TrackMaps
 
 EVAL_MEAN_KEYS = ("eval/episodic_return", "eval/episodic_return_min", "eval/episodic_return_max", "eval/episodic_length",
                   "eval/gates_per_episode", "eval/laps_per_episode", "eval/crash_rate", "eval/best_lap_steps", "eval/mean_lap_steps",
@@ -74,7 +81,7 @@ def evaluation_scalars(tot, reward_scaling, policy_range="fallback"):
 
 class Evaluator:
     def __init__(self, agent, tracks, n_envs=1024, num_rays=12, reward_scaling=0.1, device="cuda", dtype="f32", track_id=None,
-                 greedy=False, seed=0, chunk=250, rollout_kernel="auto"):
+                 greedy=False, seed=0, chunk=250, rollout_kernel="auto", track_maps=False, track_maps_cell=8):
         if int(n_envs) < 1:
             raise ValueError(f"Evaluator: n_envs must be >= 1, not {n_envs!r}")
         if int(chunk) < 1:
@@ -104,6 +111,11 @@ class Evaluator:
         self._mega_rows = None
         if self._mega:
             self._alloc_mega()
+        self.maps = self._map_track_id = self._obs_rows = None
+        if track_maps:
+            self.maps = TrackMaps(len(self.envs._tracks), track_maps_cell, self.device)
+            if self.envs._track_id is not None:
+                self._map_track_id = torch.from_numpy(self.envs._track_id).to(self.device)
 
     def _alloc_mega(self):
         N, D, C = self.num_envs, self.envs.obs_dim, self.chunk
@@ -135,6 +147,12 @@ class Evaluator:
                                     T, self.num_envs, layout, self.reward_scaling, self.state.data_ptr(), self._stream()),
               "pc_first_episodes")
 
+    def _map(self, obs, T, layout):
+        """This window's rows into the maps, BEFORE its scan: the state says which envs are still in their first episode."""
+        buffer = layout == PC_EPISODE_BUFFER
+        self.maps.update(obs[:T], self._term[:T], self._trunc[:T], self._next_term if buffer else None,
+                         self._next_trunc if buffer else None, layout, self._map_track_id, first_state=self.state)
+
     def _window_mega(self, h, T, offset):
         """pc_rollout (greedy: pc_rollout_greedy) over T steps: rows in the Buffer layout.  False = the shape is outside the persistent
         kernel's menu."""
@@ -152,14 +170,24 @@ class Evaluator:
         if rc == _capi.PC_ERR_UNSUPPORTED:
             return False
         check(rc, "pc_rollout_greedy" if self.greedy else "pc_rollout")
+        if self.maps is not None:
+            self._map(m["obs"], T, PC_EPISODE_BUFFER)
         self._scan(T, PC_EPISODE_BUFFER)
         return True
 
     def _window_steps(self, h, T, offset):
-        """T x (policy step; env step): rows in the step layout, the observation stepped in place."""
+        """T x (policy step; env step): rows in the step layout, the observation stepped in place (with maps: through the window's rows)."""
         N, di, st = self.num_envs, self.device.index, self._stream()
         obs, act = self._next_obs, self._act
+        rows = None
+        if self.maps is not None:
+            if self._obs_rows is None:
+                self._obs_rows = torch.empty(self.chunk, N, self.envs.obs_dim, dtype=torch.float32, device=self.device)
+            rows = self._obs_rows
+            rows[0].copy_(self._next_obs)
         for t in range(T):
+            if rows is not None:
+                obs = rows[t]
             if h is not None and self.greedy:       # the argmax inside the policy step: two launches per step, no logits buffer
                 check(lib.pc_policy_act_greedy(h, obs.data_ptr(), N, self._image.data_ptr(), act.data_ptr(), None, self._logprob.data_ptr(),
                                                self._val.data_ptr(), None, st), "pc_policy_act_greedy")
@@ -173,7 +201,10 @@ class Evaluator:
                 else:
                     check(lib.pc_sample(di, lg.data_ptr(), N, lg.shape[1], self.seed, offset + t, act.data_ptr(), self._logprob.data_ptr(),
                                         None, st), "pc_sample")
-            self.envs.step(act, out=(obs, self._rew[t], self._term[t], self._trunc[t]))
+            nxt = obs if rows is None else (rows[t + 1] if t + 1 < T else self._next_obs)
+            self.envs.step(act, out=(nxt, self._rew[t], self._term[t], self._trunc[t]))
+        if rows is not None:
+            self._map(rows, T, PC_EPISODE_STEPS)
         self._scan(T, PC_EPISODE_STEPS)
 
     @torch.no_grad()
@@ -184,6 +215,8 @@ class Evaluator:
         self._next_term.zero_()
         self._next_trunc.zero_()
         self.state.copy_(self._state0)
+        if self.maps is not None:
+            self.maps.clear()
         base = int(index) * PC_TIME_LIMIT
         mega = self._mega
         for t0 in range(0, PC_TIME_LIMIT, self.chunk):

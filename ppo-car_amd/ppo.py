@@ -27,6 +27,7 @@ from .buffer import Buffer
 from .env import VecCarEnv
 from .episodes import EpisodeStats, episode_scalars
 from .evaluation import EVAL_TOTALS, Evaluator
+from .track_maps import TrackMaps
 from .model import Agent
 
 
@@ -124,12 +125,25 @@ class PPOConfig:
     eval_rollout_kernel: str = "auto"      # how evaluations step: "mega" = persistent launches (greedy: pc_rollout_greedy), "steps" = the per-step
                                            # kernels, "auto" = mega for sampled evaluations, steps for greedy ones; rollout_kernel = "steps" forces "steps"
     eval_track: str | list | None = None   # the track(s) evaluated on; None = `track` (with track_interleave); another file = a held-out track
+    track_maps: bool = False               # telemetry maps of the training rollouts (ppo_car_amd.TrackMaps): per track and cell of track_maps_cell
+                                           # pixels, visits, summed speed and crashes, accumulated over epochs by ONE launch per epoch that only reads
+                                           # the rollout buffer (pc_track_maps; training computes the same bits with it on or off).  Rank 0 maps its
+                                           # own shard.  Trainer.save_track_maps writes them; off: not one launch, tensor or checkpoint key is added
+    track_maps_cell: int = 8               # cell size in pixels: 4, 5, 8, 10, 16, 20, 40 or 80
+    track_maps_every: int = 0              # train.py: K > 0 writes track_maps_<epoch> (.npz + PNGs) every K-th epoch and clears the maps, so that
+                                           # each file covers K epochs; 0 = one file at the end of the run
+    eval_track_maps: bool = False          # with eval_every: the evaluator keeps maps of its first episodes (Evaluator(track_maps=True), cell size
+                                           # track_maps_cell); train.py writes eval_track_maps_<epoch> after each evaluation
 
     def __post_init__(self):
         if self.eval_every < 0:
             raise ValueError(f"PPOConfig.eval_every must be >= 0 (0 = off), not {self.eval_every!r}")
         if self.eval_envs < 1:
             raise ValueError(f"PPOConfig.eval_envs must be >= 1, not {self.eval_envs!r}")
+        if self.track_maps_cell not in _capi.PC_MAP_CELLS:
+            raise ValueError(f"PPOConfig.track_maps_cell must be one of {_capi.PC_MAP_CELLS}, not {self.track_maps_cell!r}")
+        if self.track_maps_every < 0:
+            raise ValueError(f"PPOConfig.track_maps_every must be >= 0 (0 = only at the end of the run), not {self.track_maps_every!r}")
         if self.eval_rollout_kernel not in ("auto", "mega", "steps"):
             raise ValueError(f"PPOConfig.eval_rollout_kernel must be 'auto', 'mega' or 'steps', not {self.eval_rollout_kernel!r}")
         if self.truncation_bootstrap not in ("reference", "final_obs"):
@@ -906,7 +920,14 @@ class Trainer:
                                        device=self.device, dtype=cfg.env_dtype,
                                        track_id=mixed_track_ids(ev_track, cfg.eval_envs, cfg.track_interleave),
                                        greedy=cfg.eval_greedy, seed=cfg.seed * 1000003 + 0x9E3779B9,
-                                       rollout_kernel="steps" if cfg.rollout_kernel == "steps" else cfg.eval_rollout_kernel)
+                                       rollout_kernel="steps" if cfg.rollout_kernel == "steps" else cfg.eval_rollout_kernel,
+                                       track_maps=cfg.eval_track_maps, track_maps_cell=cfg.track_maps_cell)
+        # track_maps: rank 0 maps its own shard (the evaluator's rule: no collective); the handle's track ids are uploaded once
+        self.track_maps = self._map_track_id = None
+        if cfg.track_maps and rank == 0 and self.device.type == "cuda":
+            self.track_maps = TrackMaps(len(self.envs._tracks), cfg.track_maps_cell, self.device)
+            if track_id is not None:
+                self._map_track_id = torch.from_numpy(track_id).to(self.device)
 
     # ---- train.py:173-195 ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -1053,6 +1074,9 @@ class Trainer:
                 check(lib.pc_explained_variance(self.device.index, buf.val_buf.data_ptr(), ret.data_ptr(), ret.numel(), self._ev_ws.data_ptr(),
                                                 self._ev_out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
                       "pc_explained_variance")
+            if self.track_maps is not None:   # this rollout's rows into the maps: one launch that reads obs_buf and the flag rows, outside any capture
+                self.track_maps.update(buf.obs_buf, buf.term_buf, buf.trunc_buf, self.next_term, self.next_trunc,
+                                       track_id=self._map_track_id)
         obs, act, _val, logprob = buf.get()                                                      # :206
         self.learner.update(obs.view(-1, *self.obs_dim), act.view(-1), logprob.view(-1), adv.view(-1), ret.view(-1))
         self._aux_valid = False     # the in-kernel bootstrap values belong to THAT rollout and THOSE parameters only
@@ -1170,7 +1194,19 @@ class Trainer:
                 "rng_base": self.rng_base, "np_rng": L._np_rng.bit_generator.state, "epoch": self.epoch,
                 "global_step_idx": self.global_step_idx, "agent_rng_offset": self.agent._rng_offset,
                 "elapsed": time.time() - self.start_time, "config": dataclasses.asdict(self.cfg),
-                **({"episodes": self.episodes.state_dict()} if self.episodes is not None else {})}
+                **({"episodes": self.episodes.state_dict()} if self.episodes is not None else {}),
+                **({"track_maps": self.track_maps.state_dict()} if self.track_maps is not None else {})}
+
+    def save_track_maps(self, path_prefix, clear=False):
+        """The training maps -> <path_prefix>.npz + PNGs (TrackMaps.save; synchronises); clear: start the next file from zero."""
+        files = self.track_maps.save(path_prefix, self.envs._tracks)
+        if clear:
+            self.track_maps.clear()
+        return files
+
+    def save_eval_track_maps(self, path_prefix):
+        """The maps of the last evaluation's first episodes (eval_track_maps)."""
+        return self.evaluator.maps.save(path_prefix, self.evaluator.envs._tracks)
 
     def load_state_dict(self, sd):
         L = self.learner
@@ -1192,6 +1228,8 @@ class Trainer:
             self.rng_base.copy_(sd["rng_base"])
             if self.episodes is not None:       # a checkpoint without statistics: the episodes in progress have an unknown start
                 self.episodes.load_state_dict(sd["episodes"]) if "episodes" in sd else self.episodes.forget()
+            if self.track_maps is not None:     # a checkpoint without maps: they start from zero
+                self.track_maps.load_state_dict(sd["track_maps"]) if "track_maps" in sd else self.track_maps.clear()
         L._np_rng.bit_generator.state = sd["np_rng"]
         L._opt_started = True
         self.epoch, self.global_step_idx = sd["epoch"], sd["global_step_idx"]

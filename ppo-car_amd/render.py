@@ -9,6 +9,8 @@ import numpy as np
 WIDTH, HEIGHT = 1280, 720
 COLORS = {"background": (24, 24, 28), "wall": (235, 235, 235), "gate": (60, 110, 60), "next_gate": (90, 230, 90),
           "ray": (70, 110, 200), "car": (240, 80, 60)}
+# heatmap's fixed ramp, low to high (equally spaced stops, linear in between)
+RAMP = ((40, 40, 110), (40, 130, 200), (60, 190, 120), (240, 220, 70), (230, 60, 40))
 
 
 def _line(img, x0, y0, x1, y1, color):
@@ -44,6 +46,37 @@ def rasterise(walls, gates, px, py, rot_deg, ray_obs, next_gate=0, num_rays_nomi
         _line(img, (px + lx * c - ly * s_) * sx, (py + lx * s_ + ly * c) * sy, nose[0] * sx, nose[1] * sy, COLORS["car"])
     _line(img, (px - 8 * c + 6 * s_) * sx, (py - 8 * s_ - 6 * c) * sy, (px - 8 * c - 6 * s_) * sx, (py - 8 * s_ + 6 * c) * sy,
           COLORS["car"])
+    return img
+
+
+def heatmap(values, walls, gates, size=(1280, 720), log=True):
+    """values [GH, GW]: one number per cell of a grid over the 1280 x 720 frame (TrackMaps: visits, mean speed, crashes), coloured on
+    the fixed ramp RAMP from the smallest to the largest value present (log: on a logarithmic scale, values <= 0 are no data); cells
+    without data (NaN) keep the background colour.  Walls and gates ([n, 4] segments, Track.geometry()) are drawn over the cells.
+    Returns uint8 [H, W, 3]."""
+    w, h = size
+    sx, sy = w / WIDTH, h / HEIGHT
+    v = np.asarray(values, np.float64)
+    gh, gw = v.shape
+    has = np.isfinite(v) & ((v > 0) if log else True)
+    cells = np.empty((gh, gw, 3), np.uint8)
+    cells[:] = COLORS["background"]
+    if has.any():
+        x = np.log(v[has]) if log else v[has]
+        lo, hi = x.min(), x.max()
+        u = (x - lo) / (hi - lo) if hi > lo else np.full(x.shape, 0.5)
+        ramp = np.asarray(RAMP, np.float64)
+        pos = u * (len(ramp) - 1)
+        i = np.minimum(pos.astype(np.int64), len(ramp) - 2)
+        f = (pos - i)[:, None]
+        cells[has] = np.rint(ramp[i] * (1.0 - f) + ramp[i + 1] * f).astype(np.uint8)
+    ys = np.minimum(np.arange(h) * gh // h, gh - 1)
+    xs = np.minimum(np.arange(w) * gw // w, gw - 1)
+    img = cells[ys[:, None], xs[None, :]]
+    for g in np.asarray(gates):
+        _line(img, g[0] * sx, g[1] * sy, g[2] * sx, g[3] * sy, COLORS["gate"])
+    for s in np.asarray(walls):
+        _line(img, s[0] * sx, s[1] * sy, s[2] * sx, s[3] * sy, COLORS["wall"])
     return img
 
 

@@ -14,3 +14,4 @@ from .buffer import Buffer  # noqa: E402,F401
 from .episodes import EpisodeStats  # noqa: E402,F401
 from .model import Agent, PolicyRangeError, layer_init  # noqa: E402,F401
 from .evaluation import Evaluator  # noqa: E402,F401
+from .track_maps import TrackMaps  # noqa: E402,F401

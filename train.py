@@ -72,6 +72,13 @@ def parse_args(argv=None):
                    help="how evaluations step: 'mega' = persistent launches (with --eval-greedy: pc_rollout_greedy), 'steps' = the per-step "
                    "kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
     p.add_argument("--eval-track", default=None, help="track JSON to evaluate on (default: --track; another file = a held-out track)")
+    p.add_argument("--track-maps", action="store_true", help="accumulate telemetry maps of the training rollouts -- per track and cell: visits, "
+                   "mean speed, crashes (ppo_car_amd.TrackMaps, one extra launch per epoch) -- and write track_maps_<epoch>.npz + PNGs beside the checkpoints")
+    p.add_argument("--track-maps-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the maps in pixels")
+    p.add_argument("--track-maps-every", type=int, default=0, help="write the maps every this many epochs and clear them (each file then covers "
+                   "that many epochs); 0 = one file at the end of the run")
+    p.add_argument("--eval-track-maps", action="store_true", help="with --eval-every: maps of each evaluation's first episodes, written as "
+                   "eval_track_maps_<epoch>.npz + PNGs beside the checkpoints")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -117,7 +124,9 @@ def main(argv=None):
                     episode_stats=args.episode_stats, truncation_bootstrap=args.truncation_bootstrap,
                     update_diagnostics=args.update_diagnostics, target_kl=args.target_kl,
                     large_minibatch=args.large_minibatch, eval_every=args.eval_every, eval_envs=args.eval_envs,
-                    eval_greedy=args.eval_greedy, eval_track=args.eval_track, eval_rollout_kernel=args.eval_rollout_kernel)
+                    eval_greedy=args.eval_greedy, eval_track=args.eval_track, eval_rollout_kernel=args.eval_rollout_kernel,
+                    track_maps=args.track_maps, track_maps_cell=args.track_maps_cell, track_maps_every=args.track_maps_every,
+                    eval_track_maps=args.eval_track_maps)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
@@ -154,6 +163,10 @@ def main(argv=None):
             if rank == 0:
                 if scalars is not None:
                     report(epoch - 1 if lazy else epoch, scalars)
+                if trainer.track_maps is not None and (epoch == args.n_epochs or (args.track_maps_every > 0 and epoch % args.track_maps_every == 0)):
+                    trainer.save_track_maps(os.path.join(ckpt_dir, f"track_maps_{epoch}"), clear=True)     # (this file: the epochs since the last one)
+                if args.eval_track_maps and trainer.evaluator is not None and epoch % args.eval_every == 0:
+                    trainer.save_eval_track_maps(os.path.join(ckpt_dir, f"eval_track_maps_{epoch}"))
                 if epoch % 10 == 0:                                                                # train.py:280-283
                     torch.save(trainer.agent.state_dict(), os.path.join(ckpt_dir, f"checkpoint_{epoch}.dat"))
             if epoch % 10 == 0:   # full resumable state next to the reference-format file (every rank: env shards differ)
