@@ -10,6 +10,9 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
     python evaluate.py --checkpoint ... --envs 4096 --greedy --rollout-kernel mega     # ... the greedy windows as persistent launches
     python evaluate.py --checkpoint ... --envs 4096 --maps out/eval                    # ... plus telemetry maps of those first episodes:
                                                                      # out/eval.npz and a PNG per plane (visits, mean speed, crashes)
+    python evaluate.py --checkpoint ... --landscape out/eval [--landscape-cell 8] [--landscape-speed 0.5]
+                                                                     # the policy landscape (ppo_car_amd.PolicyLandscape): value and greedy action
+                                                                     # at every cell x 72 headings -> out/eval_landscape.npz and a PNG per track
 """
 import argparse
 import json
@@ -34,6 +37,11 @@ def parse_args(argv=None):
                     "the per-step kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
     ap.add_argument("--maps", default=None, metavar="PREFIX", help="--envs: write telemetry maps of the first episodes (ppo_car_amd.TrackMaps: "
                     "visits, mean speed and crashes per cell) to PREFIX.npz and PREFIX_<track>_<plane>.png")
+    ap.add_argument("--landscape", default=None, metavar="PREFIX", help="write the policy landscape (ppo_car_amd.PolicyLandscape: the critic's value, "
+                    "the greedy action and whether the pose is drivable, per cell and heading) to PREFIX_landscape.npz and "
+                    "PREFIX_landscape_<track>.png, instead of running episodes")
+    ap.add_argument("--landscape-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the landscape in pixels")
+    ap.add_argument("--landscape-speed", type=float, default=0.5, help="speed of the observed car as a fraction of max_speed, along its heading")
     return ap.parse_args(argv)
 
 
@@ -42,6 +50,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs the GPU: the env has no CPU path")
     import ppo_car_amd as pc
+    if args.landscape is not None:
+        return landscape(pc, args)
     if args.envs is not None:
         return batched(pc, args)
     torch.manual_seed(args.seed)
@@ -104,6 +114,23 @@ def batched(pc, args):
             out["maps"] = ev.maps.save(args.maps, ev.envs._tracks)
     finally:
         ev.close()
+    print(json.dumps(out))
+    return out
+
+
+def landscape(pc, args):
+    """--landscape PREFIX: value / action / drivable maps of the checkpoint's policy over the whole track."""
+    from ppo_car_amd.env import ray_count
+    agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
+    agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
+    ls = pc.PolicyLandscape(agent, args.track, args.num_rays, cell_px=args.landscape_cell, speed=args.landscape_speed, device="cuda")
+    try:
+        files = ls.compute().save(args.landscape)
+        best = ls.best_value()
+        out = {"landscape": files, "cells": int(best.numel()), "drivable_cells": int((~best.isnan()).sum()),
+               "poses": ls.n_tracks * ls.poses_per_track, "drivable_poses": int(ls.drivable.sum())}
+    finally:
+        ls.close()
     print(json.dumps(out))
     return out
 

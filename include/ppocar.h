@@ -136,6 +136,34 @@ int pc_env_last_step_kernel(const pc_env* e);
  * the finished episode's count is pc_env_step's `gates_passed`).  [N] int32 device arrays, either may be NULL. */
 int pc_env_info(pc_env* e, int32_t* gates_passed, int32_t* time_passed, void* stream);
 
+/* ---- observing without stepping (opt-in: the entry points above are untouched): CarEnv._get_obs (car_env.py:569-597) and
+ * Car.check_collision (car_env.py:376-392) for poses the caller names.  One launch of one kernel; the env state is neither read
+ * (pc_env_observe_poses) nor written (both).  Every ray is measured against the track's WHOLE wall list in float64 -- poses may
+ * lie on a wall, on a vertex or outside the track --, F32 handles by the float64 chain scan the step's refinement falls back to,
+ * which reports the bits the step reports: pc_env_observe right after a pc_env_step returns that step's observation, bit for
+ * bit (an env the step auto-reset shows its reset observation).  F64 handles: the reference's own arithmetic.
+ * pc_env_observe_poses: M poses, all DEVICE arrays of M entries.  M is independent of the handle's n_envs.
+ *   px, py      float64 position in pixels (Car.position); any value, the frame is not enforced (car_env.py:578-579 do not either)
+ *   vx, vy      float64 velocity in px per step, or NULL = 0: only entries 2-3 of the observation depend on it (:580-581)
+ *   turns       int32: the heading is the track's start angle + 5 degrees * turns (Car.move_car only ever adds +-5.0,
+ *               car_env.py:440-442).  F32 handles take any count (the heading tables are periodic in 72).  F64 handles: a count in
+ *               -1000 .. 1000 (an episode makes at most PC_TIME_LIMIT turns) means the float64 rotation the start angle becomes after
+ *               that many turns ONE way, every sum rounded as Car.move_car rounds it; each of them is a row of the handle's rotation
+ *               table, so cos / sin are glibc's, the reference's bits.  (A car that turned both ways can hold a rotation a few ulps
+ *               from it.)  A count outside that range takes start_angle + 5.0 * turns through the angle hash where it holds the
+ *               angle and the device's cos / sin otherwise (last-place differences from glibc are possible there).
+ *   track_id    uint8, or NULL = track 0.  A pose whose track_id >= the handle's track count gets a row of zeros and collides = 0.
+ *   obs         [M][D] float32: entries 0-3 = x / 1280, y / 720, vx / 10, vy / 10 (:578-581), 4-5 = cos / sin of the heading
+ *               (:584-588), 6 .. = each ray's min(distance, 1000) / 1000 (:590-595)
+ *   collides    [M] uint8 or NULL: 1 iff one of check_collision's rays, r in range(0, n, n // 4) (:389), is shorter than 10 px (:390)
+ * pc_env_observe: the same for the handle's CURRENT state, obs [n_envs][D], collides [n_envs] or NULL; the heading is taken from
+ *   the state as pc_env_step takes it.  The state is not modified.
+ * Checked before any device call, in this order: NULL handle, NULL px / py / turns / obs or M < 1 (pc_env_observe: NULL handle or
+ * obs): PC_ERR_INVALID_ARG; then as pc_env_step.  Neither call synchronises. */
+int pc_env_observe_poses(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy,
+                         const int32_t* turns, const uint8_t* track_id, int64_t M, float* obs, uint8_t* collides, void* stream);
+int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream);
+
 /* Per-handle launch options of pc_rollout (below).  Every choice gives bit-identical buffers; they exist so that the variant a
  * benchmark size takes can be checked at other batch sizes, and for A/B timing.
  *   PC_OPT_ROLLOUT_FORM  -1 (default) automatic: above 8192 envs independent waves of 32 envs, 256 envs per workgroup (128 up to

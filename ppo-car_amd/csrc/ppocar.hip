@@ -76,6 +76,7 @@
 // ---- the kernels, in dependency order (one translation unit: every kernel is compiled with this file's flags) ----
 #include "kernels/env_math.hpp"
 #include "kernels/env_step.hpp"
+#include "kernels/observe.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
@@ -268,6 +269,8 @@ struct pc_env {
     bool f64_offgrid = false;      // F64: pc_env_set_state left an env whose episode can leave the rotation table (a rotation that is not a
                                    // row, or a row more turns from start_rot than the env's time step): the selector kernel needs rows
     DevBuf<float> reset_obs;
+    DevBuf<int> turn_row;          // F64: per track and turn count -PC_OBSERVE_TURNS .. PC_OBSERVE_TURNS, the row of the rotation table that holds
+                                   // start_rot after that many turns one way (-1: none) -- pc_env_observe_poses' headings
 
     template <typename T> EnvParams<T> params() const {
         EnvParams<T> p;
@@ -524,6 +527,28 @@ static int greedy_small(int KS, int rpl, bool epw16, bool rden, RolloutLaunch& o
     return PC_OK;
 }
 
+// K17: lanes per pose -- enough to fill the device at small M (the rule of choose_geometry), never more than rays, one at large M; the
+// handle's pc_env_set_lanes_per_env override applies (every choice writes the same bytes: a ray's value does not depend on its lane)
+template <typename T, bool STATE>
+static int observe_launch(const pc_env* e, ObservePoses q, float* obs, uint8_t* collides, hipStream_t st) {
+    int G = 1;
+    if (e->lanes_override > 0) {
+        while (2 * G <= e->lanes_override && 2 * G <= e->R) G <<= 1;
+    } else {
+        while (2 * G <= e->R && G < 64 && (int64_t)G * q.M < 262144) G <<= 1;
+    }
+    q.lg = 0;
+    while ((1 << q.lg) < G) ++q.lg;
+    q.n_tracks = e->n_tracks;
+    q.turn_row = e->turn_row;
+    if (q.M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
+    const int64_t blocks = ((q.M << q.lg) + 255) / 256;
+    if (blocks > INT_MAX) return PC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((observe_kernel<T, STATE>), dim3((unsigned)blocks), dim3(256), 0, st, e->params<T>(), q, obs, collides);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
 extern "C" {
 
 const char* pc_strerror(int code) {
@@ -615,6 +640,24 @@ static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8
     e->rot_ids = std::move(tt.rot_ids);
     e->rot_depth = std::move(tt.rot_depth);
     e->facts = tt.facts;
+    std::vector<int> turn_row;
+    if (f64) {      // pc_env_observe_poses: the rotation a turn count means = start_rot after that many turns ONE way, each sum rounded
+                    // (car_env.py:440-442); the table holds every one of them (its breadth-first depth is the count)
+        turn_row.assign((size_t)e->n_tracks * (2 * PC_OBSERVE_TURNS + 1), -1);
+        for (int k = 0; k < e->n_tracks; ++k) {
+            if (e->hdr_host[k].rot_off < 0) continue;
+            int* row = turn_row.data() + (size_t)k * (2 * PC_OBSERVE_TURNS + 1) + PC_OBSERVE_TURNS;
+            for (const double step : {5.0, -5.0}) {
+                double rot = e->hdr_host[k].start_rot;
+                for (int t = 0; t <= PC_OBSERVE_TURNS; ++t, rot += step) {
+                    uint64_t b;
+                    std::memcpy(&b, &rot, 8);
+                    const auto it = e->rot_ids[k].find(b);
+                    row[step > 0 ? t : -t] = it != e->rot_ids[k].end() ? it->second : -1;
+                }
+            }
+        }
+    }
     // ---- device buffers
     const size_t N = (size_t)e->N;
     HIPCHK(e->pv.alloc(N));
@@ -637,6 +680,7 @@ static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8
     HIPCHK(e->dirtab64.upload(tt.dirtab64));
     HIPCHK(e->seg64.upload(tt.seg64));
     HIPCHK(e->dirhash.upload(tt.dirhash));
+    HIPCHK(e->turn_row.upload(turn_row));
     HIPCHK(e->rden.alloc(tt.rden_floats ? tt.rden_floats : 1));
     hipLaunchKernelGGL(rden_build_kernel, dim3(64), dim3(256), 0, 0, e->params<float>(), e->n_tracks, e->rden.p);
     HIPCHK(hipGetLastError());
@@ -780,6 +824,29 @@ int pc_env_step_many(pc_env* e, const int64_t* actions, int64_t T, double reward
 }
 
 int pc_env_last_step_kernel(const pc_env* e) { return e ? e->last_step_kernel : PC_ERR_INVALID_ARG; }
+
+int pc_env_observe_poses(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
+                         const uint8_t* track_id, int64_t M, float* obs, uint8_t* collides, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e || !px || !py || !turns || !obs || M < 1) return PC_ERR_INVALID_ARG;      // (before the handle is looked at)
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    ObservePoses q{};
+    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.track_id = track_id; q.M = M;
+    return e->dtype == PC_DTYPE_F64 ? observe_launch<double, false>(e, q, obs, collides, (hipStream_t)stream)
+                                    : observe_launch<float, false>(e, q, obs, collides, (hipStream_t)stream);
+}
+
+int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e || !obs) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    ObservePoses q{};
+    q.M = e->N;
+    return e->dtype == PC_DTYPE_F64 ? observe_launch<double, true>(e, q, obs, collides, (hipStream_t)stream)
+                                    : observe_launch<float, true>(e, q, obs, collides, (hipStream_t)stream);
+}
 
 int pc_env_info(pc_env* e, int32_t* gates_passed, int32_t* time_passed, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)

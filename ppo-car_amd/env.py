@@ -288,6 +288,33 @@ class VecCarEnv:
             self._episodes.update(rew, term, trunc, layout="steps")
         return obs, rew, term, trunc
 
+    # ---- observing without stepping (pc_env_observe, pc_env_observe_poses) ---------------------------------------------------
+    def observe(self, out=None, collides=None):
+        """CarEnv._get_obs() (car_env.py:569-597) of every env's CURRENT state: obs [N, D] float32, e.g. after set_state().  Right
+        after step() it is that step's observation, bit for bit.  collides: an optional [N] uint8 tensor that receives
+        Car.check_collision (car_env.py:376-392).  The state is not modified; one launch, no synchronisation."""
+        N, D = self.num_envs, self.obs_dim
+        obs = out if out is not None else self._new(N, D)
+        check(lib.pc_env_observe(self._h, self._ptr(obs, torch.float32, N * D, "obs"), self._ptr(collides, torch.uint8, N, "collides"),
+                                 self._stream()), "pc_env_observe")
+        return obs
+
+    def observe_poses(self, px, py, turns, vx=None, vy=None, track_id=None, out=None, collides=None):
+        """What a car at each of M poses sees on this env's tracks: obs [M, D] float32.  px, py (and vx, vy, default 0) float64,
+        turns int32 (heading = the track's start angle + 5 degrees * turns), track_id uint8 (default track 0): device tensors of M
+        entries, M independent of num_envs.  collides: an optional [M] uint8 tensor for Car.check_collision.  A pose whose track_id
+        this env does not have gets a row of zeros.  The env state is neither read nor written; one launch, no synchronisation."""
+        if px.dim() != 1 or px.numel() < 1:
+            raise ValueError(f"observe_poses: px must be a 1-d tensor of M >= 1 poses, got {tuple(px.shape)}")
+        M, D = px.numel(), self.obs_dim
+        obs = out if out is not None else self._new(M, D)
+        check(lib.pc_env_observe_poses(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
+                                       self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
+                                       self._ptr(turns, torch.int32, M, "turns"), self._ptr(track_id, torch.uint8, M, "track_id"), M,
+                                       self._ptr(obs, torch.float32, M * D, "obs"), self._ptr(collides, torch.uint8, M, "collides"),
+                                       self._stream()), "pc_env_observe_poses")
+        return obs
+
     def last_step_kernel(self):
         """which kernel the last step() / step_many() launched: "K1" (generic per-step kernel), "K1f" (table-driven), "K1f-table" or "none"."""
         code = lib.pc_env_last_step_kernel(self._h)

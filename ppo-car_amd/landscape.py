@@ -1,0 +1,153 @@
+"""Policy landscape: what the policy would do, and what the critic expects, at every spot of the track -- the spots the cars never
+reach included.  Per track, the centre of every cell of the track maps' grid (TrackMaps: GW = 1280 // cell_px, GH = 720 // cell_px)
+is observed at all 72 headings by K17 (include/ppocar.h pc_env_observe_poses) with the car driving where it points, and the greedy
+policy step (pc_policy_act_greedy) runs on those observations.
+
+value [n_tracks, 72, GH, GW] float32 (the critic), action [.., 72, GH, GW] uint8 (the first argmax of the logits), drivable
+[.., 72, GH, GW] bool (Car.check_collision is false at the pose).  Heading index t means the track's start angle + 5 t degrees.
+compute() only enqueues (observe, act, two copies per chunk of at most 2^18 poses), draws no random number and writes nothing
+but its own tensors: a training run computes the same bits with or without it."""
+import os
+
+import numpy as np
+import torch
+
+from ._capi import PC_MAP_CELLS
+
+WIDTH, HEIGHT, MAX_SPEED = 1280, 720, 10.0       # the frame (car_env.py:578-579) and the speed limit per axis in px per step (:580-581)
+HEADINGS, TURN_DEG = 72, 5.0                     # Car.move_car turns by 5 degrees (car_env.py:440-442): 72 headings
+CHUNK = 1 << 18                                  # poses per observe / act launch pair
+NO_ACTION = 255                                  # action_at_best() where no heading is drivable
+
+
+def grid_poses(start_angle, cell_px, speed):
+    """The poses of one track, as float64 / int32 numpy arrays of 72 * GH * GW entries in [heading][cy][cx] order: the cell centres
+    ((cx + 0.5) * cell_px, (cy + 0.5) * cell_px), turns 0 .. 71, and the velocity speed * max_speed along the heading start_angle +
+    5 * turns degrees (cosine and sine in float64 on the host).  Returns px, py, vx, vy, turns."""
+    GH, GW = HEIGHT // cell_px, WIDTH // cell_px
+    turns = np.arange(HEADINGS, dtype=np.int32)
+    a = np.radians(np.float64(start_angle) + TURN_DEG * turns.astype(np.float64))
+    shape = (HEADINGS, GH, GW)
+    px = np.broadcast_to(((np.arange(GW, dtype=np.float64) + 0.5) * cell_px)[None, None, :], shape)
+    py = np.broadcast_to(((np.arange(GH, dtype=np.float64) + 0.5) * cell_px)[None, :, None], shape)
+    vx = np.broadcast_to((np.float64(speed) * MAX_SPEED * np.cos(a))[:, None, None], shape)
+    vy = np.broadcast_to((np.float64(speed) * MAX_SPEED * np.sin(a))[:, None, None], shape)
+    tn = np.broadcast_to(turns[:, None, None], shape)
+    return tuple(np.ascontiguousarray(x).reshape(-1) for x in (px, py, vx, vy, tn))
+
+
+def best_value(value, drivable):
+    """[72, GH, GW] -> [GH, GW]: the largest value over the drivable headings, NaN where no heading is drivable."""
+    v = torch.where(drivable, value, torch.full_like(value, float("-inf"))).amax(0)
+    return torch.where(drivable.any(0), v, torch.full_like(v, float("nan")))
+
+
+def best_turn(value, drivable):
+    """[72, GH, GW] -> [GH, GW] int64: the first heading index at that maximum; -1 where no heading is drivable."""
+    t = torch.where(drivable, value, torch.full_like(value, float("-inf"))).argmax(0)
+    return torch.where(drivable.any(0), t, torch.full_like(t, -1))
+
+
+class PolicyLandscape:
+    def __init__(self, agent, tracks, num_rays, cell_px=8, speed=0.5, dtype="f32", device="cuda", envs=None):
+        """agent: ppo_car_amd.Agent (its act(obs, greedy=True)); tracks: one path / Track or a list; num_rays: Car's nominal ray
+        count, which fixes the agent's input width.  The landscape owns a one-env handle, used for its track tables only.  (envs: an
+        object with observe_poses(), obs_dim and _tracks to use in its place -- the host tests' stand-in.)"""
+        if cell_px not in PC_MAP_CELLS:
+            raise ValueError(f"PolicyLandscape: cell_px must be one of {PC_MAP_CELLS}, not {cell_px!r}")
+        if not 0.0 <= float(speed) <= 1.0:
+            raise ValueError(f"PolicyLandscape: speed is a fraction of max_speed, 0 .. 1, not {speed!r}")
+        self.agent, self.cell_px, self.speed = agent, int(cell_px), float(speed)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._own_envs = envs is None
+        if envs is None:
+            from .env import VecCarEnv
+            envs = VecCarEnv(1, tracks, num_rays=num_rays, device=self.device, dtype=dtype)
+        self.envs = envs
+        self.tracks = list(envs._tracks)
+        self.n_tracks = len(self.tracks)
+        self.grid = (HEIGHT // self.cell_px, WIDTH // self.cell_px)         # (GH, GW)
+        self.poses_per_track = HEADINGS * self.grid[0] * self.grid[1]
+        # the poses of every track, [n_tracks * poses_per_track] each: constant, uploaded once
+        cols = [grid_poses(t.start_angle, self.cell_px, self.speed) for t in self.tracks]
+        self._px, self._py, self._vx, self._vy, self._turns = (
+            torch.from_numpy(np.concatenate([c[i] for c in cols])).to(self.device) for i in range(5))
+        self._track_id = torch.arange(self.n_tracks, dtype=torch.uint8).repeat_interleave(self.poses_per_track).to(self.device)
+        shape = (self.n_tracks, HEADINGS, *self.grid)
+        self.value = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.action = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        self.drivable = torch.zeros(shape, dtype=torch.bool, device=self.device)
+        n = min(CHUNK, self.n_tracks * self.poses_per_track)
+        self._obs = torch.empty(n, envs.obs_dim, dtype=torch.float32, device=self.device)
+        self._act = torch.empty(n, dtype=torch.int64, device=self.device)
+        self._logprob = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._collides = torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    def poses(self):
+        """(px, py, vx, vy, turns, track_id): the device tensors compute() evaluates, [n_tracks * 72 * GH * GW] each."""
+        return self._px, self._py, self._vx, self._vy, self._turns, self._track_id
+
+    def compute(self):
+        """Fill value / action / drivable from the agent's current weights.  Per chunk of at most 2^18 poses: one
+        pc_env_observe_poses launch and one pc_policy_act_greedy launch (the weights are packed once, ahead of the first).
+        Enqueues on the current stream; no synchronisation, no random draw.  Returns self."""
+        total = self.n_tracks * self.poses_per_track
+        value, action, drivable = self.value.view(-1), self.action.view(-1), self.drivable.view(-1)
+        for lo in range(0, total, CHUNK):
+            hi = min(lo + CHUNK, total)
+            n = hi - lo
+            obs, collides = self._obs[:n], self._collides[:n]
+            self.envs.observe_poses(self._px[lo:hi], self._py[lo:hi], self._turns[lo:hi], vx=self._vx[lo:hi], vy=self._vy[lo:hi],
+                                    track_id=self._track_id[lo:hi], out=obs, collides=collides)
+            self.agent.act(obs, out_action=self._act[:n], out_logprob=self._logprob[:n], out_value=value[lo:hi], greedy=True,
+                           repack=lo == 0)
+            action[lo:hi].copy_(self._act[:n])
+            torch.eq(collides, 0, out=drivable[lo:hi])
+        return self
+
+    # ---- reductions over the headings (device tensors; no host synchronisation) -------------------------------------------------
+    def best_value(self, track=0):
+        """[GH, GW] float32: the critic's value at the best drivable heading; NaN where no heading is drivable."""
+        return best_value(self.value[track], self.drivable[track])
+
+    def best_heading(self, track=0):
+        """[GH, GW] float64: that heading in degrees, the track's start angle + 5 * its index; NaN where no heading is drivable."""
+        t = best_turn(self.value[track], self.drivable[track])
+        deg = self.tracks[track].start_angle + TURN_DEG * t.to(torch.float64)
+        return torch.where(t >= 0, deg, torch.full_like(deg, float("nan")))
+
+    def action_at_best(self, track=0):
+        """[GH, GW] uint8: the greedy action at that heading; NO_ACTION (255) where no heading is drivable."""
+        t = best_turn(self.value[track], self.drivable[track])
+        a = self.action[track].gather(0, t.clamp(min=0).unsqueeze(0)).squeeze(0)
+        return torch.where(t >= 0, a, torch.full_like(a, NO_ACTION))
+
+    # ---- files -------------------------------------------------------------------------------------------------------------------
+    def save(self, path_prefix):
+        """<path_prefix>_landscape.npz (value, action, drivable, best_value, best_heading, action_at_best, cell_px, speed, the track
+        names) and one PNG per track, <path_prefix>_landscape_<track>.png: best_value on a linear ramp, walls and gates drawn over
+        it.  Synchronises (it fetches the tensors).  Returns the files written."""
+        from .render import heatmap, write_png
+        names = [os.path.splitext(os.path.basename(os.fspath(t.path)))[0] if getattr(t, "path", None) is not None else f"track{k}"
+                 for k, t in enumerate(self.tracks)]
+        if len(set(names)) != len(names):
+            names = [f"{k}_{n}" for k, n in enumerate(names)]
+        os.makedirs(os.path.dirname(os.path.abspath(path_prefix)), exist_ok=True)
+        best = np.stack([self.best_value(k).cpu().numpy() for k in range(self.n_tracks)])
+        files = [f"{path_prefix}_landscape.npz"]
+        np.savez_compressed(files[0], value=self.value.cpu().numpy(), action=self.action.cpu().numpy(), drivable=self.drivable.cpu().numpy(),
+                            best_value=best, best_heading=np.stack([self.best_heading(k).cpu().numpy() for k in range(self.n_tracks)]),
+                            action_at_best=np.stack([self.action_at_best(k).cpu().numpy() for k in range(self.n_tracks)]),
+                            cell_px=np.int64(self.cell_px), speed=np.float64(self.speed), tracks=np.array(names))
+        for k, t in enumerate(self.tracks):
+            walls, gates = t.geometry()
+            files.append(f"{path_prefix}_landscape_{names[k]}.png")
+            write_png(files[-1], heatmap(best[k].astype(np.float64), walls, gates, log=False))
+        return files
+
+    def close(self):
+        if self._own_envs and self.envs is not None:
+            self.envs.close()
+        self.envs = None

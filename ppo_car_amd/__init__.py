@@ -15,3 +15,4 @@ from .episodes import EpisodeStats  # noqa: E402,F401
 from .model import Agent, PolicyRangeError, layer_init  # noqa: E402,F401
 from .evaluation import Evaluator  # noqa: E402,F401
 from .track_maps import TrackMaps  # noqa: E402,F401
+from .landscape import PolicyLandscape  # noqa: E402,F401

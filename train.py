@@ -79,6 +79,11 @@ def parse_args(argv=None):
                    "that many epochs); 0 = one file at the end of the run")
     p.add_argument("--eval-track-maps", action="store_true", help="with --eval-every: maps of each evaluation's first episodes, written as "
                    "eval_track_maps_<epoch>.npz + PNGs beside the checkpoints")
+    p.add_argument("--landscape-every", type=int, default=0, help="every this many epochs (rank 0), write the policy landscape of the updated "
+                   "policy (ppo_car_amd.PolicyLandscape: value, greedy action and drivability per cell and heading, observed without stepping) as "
+                   "landscape_<epoch>_landscape.npz + a PNG per track beside the checkpoints; 0 = never.  Training computes the same bits either way")
+    p.add_argument("--landscape-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the landscape in pixels")
+    p.add_argument("--landscape-speed", type=float, default=0.5, help="speed of the observed car as a fraction of max_speed, along its heading")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -133,6 +138,11 @@ def main(argv=None):
         path = args.resume if world == 1 else args.resume.replace(".pt", f".rank{rank}.pt")
         trainer.load_state_dict(torch.load(path, map_location=trainer.device, weights_only=False))
         first_epoch = trainer.epoch + 1             # (charts/SPS keeps counting from the checkpoint's elapsed time)
+    landscape = None
+    if rank == 0 and args.landscape_every > 0:      # (held here, not by the Trainer: off, not one launch or tensor exists)
+        from ppo_car_amd import PolicyLandscape
+        landscape = PolicyLandscape(trainer.agent, args.track, args.num_rays, cell_px=args.landscape_cell, speed=args.landscape_speed,
+                                    dtype=args.env_dtype, device=trainer.device)
     if rank == 0:
         print(trainer.agent.actor)      # train.py:148-149
         print(trainer.agent.critic)
@@ -167,6 +177,8 @@ def main(argv=None):
                     trainer.save_track_maps(os.path.join(ckpt_dir, f"track_maps_{epoch}"), clear=True)     # (this file: the epochs since the last one)
                 if args.eval_track_maps and trainer.evaluator is not None and epoch % args.eval_every == 0:
                     trainer.save_eval_track_maps(os.path.join(ckpt_dir, f"eval_track_maps_{epoch}"))
+                if landscape is not None and epoch % args.landscape_every == 0:      # after the epoch, outside any graph, no random draw
+                    landscape.compute().save(os.path.join(ckpt_dir, f"landscape_{epoch}"))
                 if epoch % 10 == 0:                                                                # train.py:280-283
                     torch.save(trainer.agent.state_dict(), os.path.join(ckpt_dir, f"checkpoint_{epoch}.dat"))
             if epoch % 10 == 0:   # full resumable state next to the reference-format file (every rank: env shards differ)
@@ -178,6 +190,8 @@ def main(argv=None):
             if last is not None:
                 report(args.n_epochs, last)
     finally:
+        if landscape is not None:
+            landscape.close()
         trainer.close()                                                                            # train.py:296
         if rank == 0:
             log.close()
