@@ -10,6 +10,9 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
     python evaluate.py --checkpoint ... --envs 4096 --greedy --rollout-kernel mega     # ... the greedy windows as persistent launches
     python evaluate.py --checkpoint ... --envs 4096 --maps out/eval                    # ... plus telemetry maps of those first episodes:
                                                                      # out/eval.npz and a PNG per plane (visits, mean speed, crashes)
+    python evaluate.py --checkpoint ... --envs 64 --video out.png [--video-envs 4] [--video-scale 4] [--video-fps 30]
+                                                                     # ... plus an animated PNG of envs 0 .. 3 driving their first episodes,
+                                                                     # rendered on the device (ppo_car_amd.Renderer), side by side
     python evaluate.py --checkpoint ... --landscape out/eval [--landscape-cell 8] [--landscape-speed 0.5]
                                                                      # the policy landscape (ppo_car_amd.PolicyLandscape): value and greedy action
                                                                      # at every cell x 72 headings -> out/eval_landscape.npz and a PNG per track
@@ -42,7 +45,28 @@ def parse_args(argv=None):
                     "PREFIX_landscape_<track>.png, instead of running episodes")
     ap.add_argument("--landscape-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the landscape in pixels")
     ap.add_argument("--landscape-speed", type=float, default=0.5, help="speed of the observed car as a fraction of max_speed, along its heading")
-    return ap.parse_args(argv)
+    ap.add_argument("--video", default=None, metavar="FILE.png", help="--envs: write an animated PNG of the first episodes of envs 0 .. --video-envs - 1 "
+                    "(every second step, rendered on the device from the evaluation's own observation rows)")
+    ap.add_argument("--video-envs", type=int, default=4, help="envs shown side by side in the video")
+    ap.add_argument("--video-scale", type=int, default=4, help="a video frame is 1280 / scale x 720 / scale per env: 1, 2, 4, 5, 8 or 10")
+    ap.add_argument("--video-fps", type=int, default=30)
+    args = ap.parse_args(argv)
+    check_video_args(args)
+    return args
+
+
+def check_video_args(args):
+    """ValueError for a --video request that cannot be served (before anything touches the device)."""
+    if args.video is None:
+        return
+    if args.envs is None:
+        raise ValueError("--video renders envs of the batched evaluation: pass --envs N")
+    if not 1 <= args.video_envs <= args.envs:
+        raise ValueError(f"--video-envs must be 1 .. --envs = {args.envs}, not {args.video_envs}")
+    if args.video_scale not in (1, 2, 4, 5, 8, 10):
+        raise ValueError(f"--video-scale must be one of 1, 2, 4, 5, 8, 10, not {args.video_scale}")
+    if not 1 <= args.video_fps <= 65535:
+        raise ValueError(f"--video-fps must be 1 .. 65535, not {args.video_fps}")
 
 
 def main(argv=None):
@@ -106,12 +130,18 @@ def batched(pc, args):
     agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
     agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     ev = pc.Evaluator(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda", greedy=args.greedy,
-                      seed=args.seed, rollout_kernel=args.rollout_kernel, track_maps=args.maps is not None)
+                      seed=args.seed, rollout_kernel=args.rollout_kernel, track_maps=args.maps is not None,
+                      video_envs=args.video_envs if args.video is not None else 0, video_scale=args.video_scale)
     try:
         out = ev.evaluate()
         out["path"] = ev.last_path
         if args.maps is not None:
             out["maps"] = ev.maps.save(args.maps, ev.envs._tracks)
+        if args.video is not None:
+            from ppo_car_amd.render import write_apng
+            frames = ev.video_frames()
+            write_apng(args.video, frames, fps=args.video_fps)
+            out["video"] = {"file": args.video, "frames": int(frames.shape[0]), "height": int(frames.shape[1]), "width": int(frames.shape[2])}
     finally:
         ev.close()
     print(json.dumps(out))

@@ -333,6 +333,56 @@ int pc_track_maps(int device, const float* obs, int64_t D, const float* term, co
                   const float* last_trunc, int64_t T, int64_t N, int layout, const uint8_t* track_id, int n_tracks, int cell_px,
                   const double* first_state, int64_t* maps, void* stream);
 
+/* ---- frames on the device (opt-in: the entry points above are untouched): CarEnv.render() in rgb_array mode (car_env.py:762-807)
+ * and log_video's frames (train.py:23-50), as a pure function of (observation row, track, next-gate index).  An observation row holds
+ * the car's position (entries 0-1), the cos / sin of its heading (4-5) and every ray's length (6 ..), so M rows that are already on the
+ * device -- a rollout or evaluation buffer -- become M RGB frames without an env, a re-simulation or a host round trip.  The look is
+ * this project's (no sprite, no anti-aliasing); the rule is exact integer arithmetic, so every pixel is defined (DESIGN.md 4.11;
+ * tests/render_reference.py is its numpy form):
+ *   grid       quarter pixels (q), int32.  W = 1280 / scale, H = 720 / scale, scale one of 1, 2, 4, 5, 8, 10; the centre of pixel (i, j)
+ *              is P = (4 scale i + 2 scale, 4 scale j + 2 scale).  Q(v) = (int32)rint(v * 4.0) on a float64 v.
+ *   static     walls and gates: pc_track_geometry's float64 pixel coordinates, each through Q.
+ *   per row o  x = (double)o[0] * 1280.0, y = (double)o[1] * 720.0, c = (double)o[4], s = (double)o[5].  Ray i of R = pc_ray_count(n):
+ *              (ci, si) = the HOST's float64 cos / sin of radians(i * (360 / n)) (a table made at pc_env_create; the device's own
+ *              cos / sin is never used), dx = c ci - s si, dy = s ci + c si, d = 1000.0 * (double)o[6 + i] clamped to [0, 1000] (a
+ *              non-finite entry: 0); the ray runs from (Q(x), Q(y)) to (Q(x + d dx), Q(y + d dy)).  The car is the capsule from
+ *              (Q(x - 8.0 c), Q(y - 8.0 s)) to (Q(x + 14.0 c), Q(y + 14.0 s)).
+ *   coverage   a segment (A, B) of half-width h covers P, with u = (P - A).(B - A) and L = |B - A|^2: L == 0 or u <= 0: |P - A|^2 <= h^2;
+ *              u >= L: |P - B|^2 <= h^2; else cross(P - A, B - A)^2 <= h^2 L.  A disc is a segment with A == B.  Half-widths in q:
+ *              max(nominal, 3 scale) with nominal 10 (wall), 10 (gate), 2 (ray), 24 (car); a hit disc has radius 20, not widened.
+ *   road       P is road iff an odd number of its track's walls have (A.y > P.y) != (B.y > P.y) and cross P's row strictly to its right:
+ *              cross(P - A, B - A) < 0 where B.y > A.y, > 0 where B.y < A.y.
+ *   layers     later wins: grass, road, walls, plain gates (in index order), the highlighted gate, rays, one hit disc at every ray's
+ *              end, the car.  With next_gate: gate g is drawn iff g >= next_gate[m] (the reference hides the gates passed in this lap,
+ *              car_env.py:725-741, 788-793) and gate next_gate[m], if the track has it, in PC_RENDER_NEXT_GATE.  NULL: all gates plain.
+ *   guards     a row draws the static layers only, every gate plain, if o[0], o[1], o[4] or o[5] is not finite, |o[4]| or |o[5]| > 1,
+ *              the car lies outside [-1024, 2304] x [-1024, 1744] px, or its track_id is not a track of the handle (track 0 is shown).
+ * pc_render_background: the static layers of every track of the handle at `scale`, once per (handle, scale):
+ *   background [n_tracks][2][H][W] uint8 (device, 4-byte aligned): plane 0 = PC_RENDER_GRASS / _ROAD / _WALL, plane 1 = 1 + the highest
+ *              gate index that covers the pixel, 0 = none.
+ * pc_render_frames: M rows -> frames [M][H][W][3] uint8 (device, 4-byte aligned; r, g, b).
+ *   obs        row m at obs + m * obs_ld, obs_ld >= D: one env's rows of a [T][N][D] buffer are obs_ld = N * D
+ *   next_gate  [M] int32 (device) or NULL;  track_id [M] uint8 (device) or NULL = track 0
+ *   background what pc_render_background wrote for the same handle and scale
+ *   palette    HOST [PC_RENDER_COLORS][3] uint8 (r, g, b per PC_RENDER_* index) or NULL = the default; copied into the launch's arguments
+ *   M is independent of the handle's env count.  Neither call reads or writes env state; neither synchronises.
+ * Checked before any device call, in this order: NULL handle / background (pc_render_frames: / obs / frames, M < 1, obs_ld < D), a
+ * scale off the list, a background or frames pointer that is not 4-byte aligned: PC_ERR_INVALID_ARG; then a handle one of whose tracks
+ * has a wall or gate coordinate outside [-1024, 2304] x [-1024, 1744] px (or not finite), or more than 255 gates: PC_ERR_UNSUPPORTED
+ * with the reason in pc_last_hip_error. */
+#define PC_RENDER_GRASS 0
+#define PC_RENDER_ROAD 1
+#define PC_RENDER_WALL 2
+#define PC_RENDER_GATE 3
+#define PC_RENDER_NEXT_GATE 4
+#define PC_RENDER_RAY 5
+#define PC_RENDER_HIT 6
+#define PC_RENDER_CAR 7
+#define PC_RENDER_COLORS 8
+int pc_render_background(const pc_env* e, int scale, uint8_t* background, void* stream);
+int pc_render_frames(const pc_env* e, const float* obs, int64_t obs_ld, const int32_t* next_gate, const uint8_t* track_id,
+                     int64_t M, int scale, const uint8_t* background, const uint8_t* palette, uint8_t* frames, void* stream);
+
 /* ---- the whole of Agent.get_action_and_value(x) as the rollout calls it (model.py:34-41, train.py:181):
  * both 1-hidden-layer MLPs (actor D->H->A, critic D->H->1, ReLU), the categorical draw, log_prob and the
  * value, in one launch on the matrix cores.  A policy step's configuration is a HANDLE: shape (D, H, A), arithmetic form of the

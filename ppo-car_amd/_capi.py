@@ -22,6 +22,9 @@ PC_FIRST_RUNNING, PC_FIRST_TERMINATED, PC_FIRST_TRUNCATED = 0, 1, 2
 PC_MAP_VISITS, PC_MAP_SPEED, PC_MAP_CRASHES, PC_MAP_PLANES = 0, 1, 2, 3     # pc_track_maps: the planes of one track (include/ppocar.h)
 PC_MAP_SPEED_UNIT = 1024          # ... SPEED is in units of max_speed / 1024
 PC_MAP_CELLS = (4, 5, 8, 10, 16, 20, 40, 80)      # ... the cell sizes in pixels it takes
+PC_RENDER_GRASS, PC_RENDER_ROAD, PC_RENDER_WALL, PC_RENDER_GATE, PC_RENDER_NEXT_GATE, PC_RENDER_RAY, PC_RENDER_HIT, PC_RENDER_CAR = range(8)     # pc_render_*: layer / colour indices (include/ppocar.h)
+PC_RENDER_COLORS = 8
+PC_RENDER_SCALES = (1, 2, 4, 5, 8, 10)            # ... frames are 1280 / scale x 720 / scale
 PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppocar.h)
 PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_TIME_LIMIT = 1000     # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
@@ -96,6 +99,8 @@ _sig = {
     "pc_first_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp]),
     "pc_greedy": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "pc_track_maps": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "pc_render_background": (_i, [_vp, _i, _vp, _vp]),
+    "pc_render_frames": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "pc_policy_create": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pc_policy_destroy": (None, [_vp]),
     "pc_policy_get": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),

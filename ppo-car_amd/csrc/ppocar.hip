@@ -80,6 +80,7 @@
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
+#include "kernels/render.hpp"
 #include "kernels/policy.hpp"
 #include "kernels/rollout.hpp"
 #include "kernels/env_steps.hpp"
@@ -269,6 +270,12 @@ struct pc_env {
     bool f64_offgrid = false;      // F64: pc_env_set_state left an env whose episode can leave the rotation table (a rotation that is not a
                                    // row, or a row more turns from start_rot than the env's time step): the selector kernel needs rows
     DevBuf<float> reset_obs;
+    // pc_render_*: the tracks' walls and gates in quarter pixels, each track's slice of them, and the rays' directions (host cos / sin);
+    // render_err: why the handle's tracks cannot be rendered (empty: they can)
+    DevBuf<int4> render_walls, render_gates;
+    DevBuf<RenderTrack> render_trk;
+    DevBuf<double2> render_dirs;
+    std::string render_err;
     DevBuf<int> turn_row;          // F64: per track and turn count -PC_OBSERVE_TURNS .. PC_OBSERVE_TURNS, the row of the rotation table that holds
                                    // start_rot after that many turns one way (-1: none) -- pc_env_observe_poses' headings
 
@@ -629,6 +636,49 @@ void pc_env_destroy(pc_env* e) {
     delete e;      // (the device buffers free themselves: DevBuf)
 }
 
+// pc_render_*: quantise the tracks' geometry (Q of include/ppocar.h) and build the rays' direction table with the host's cos / sin
+// (math.radians' product, then libm: what tests/render_reference.py evaluates).  A track the integer bounds of kernels/render.hpp do not
+// hold for leaves render_err set and the handle otherwise as it is: only the render calls refuse it.
+static int render_prepare(pc_env* e, const pc_track* const* tracks) {
+    struct Q4 { int x, y, z, w; };
+    std::vector<Q4> walls, gates;
+    std::vector<RenderTrack> trk((size_t)e->n_tracks);
+    const auto quantise = [&](const std::vector<double>& src, std::vector<Q4>& dst, int k, const char* what) {
+        for (size_t i = 0; i + 3 < src.size(); i += 4) {
+            for (int j = 0; j < 4; ++j) {
+                const double v = src[i + j], hi = (j & 1) ? 1744.0 : 2304.0;
+                if (!(std::isfinite(v) && v >= -1024.0 && v <= hi) && e->render_err.empty())
+                    e->render_err = "track " + std::to_string(k) + ": " + what + " " + std::to_string(i / 4) +
+                                    " has a coordinate outside [-1024, 2304] x [-1024, 1744] px: it cannot be rendered";
+            }
+            if (e->render_err.empty()) dst.push_back({render_q(src[i]), render_q(src[i + 1]), render_q(src[i + 2]), render_q(src[i + 3])});
+        }
+    };
+    for (int k = 0; k < e->n_tracks; ++k) {
+        trk[k].wall_off = (int)walls.size();
+        trk[k].gate_off = (int)gates.size();
+        trk[k].n_walls = tracks[k]->n_walls();
+        trk[k].n_gates = tracks[k]->n_gates();
+        if (trk[k].n_gates > 255 && e->render_err.empty())
+            e->render_err = "track " + std::to_string(k) + ": more than 255 reward gates: it cannot be rendered";
+        quantise(tracks[k]->walls, walls, k, "wall");
+        quantise(tracks[k]->gates, gates, k, "gate");
+    }
+    if (!e->render_err.empty()) return PC_OK;
+    std::vector<PairD> dirs((size_t)e->R);
+    const int step = 360 / e->n_nominal;
+    for (int i = 0; i < e->R; ++i) {
+        const double a = (double)(i * step) * (3.14159265358979323846 / 180.0);
+        dirs[i] = {std::cos(a), std::sin(a)};
+    }
+    static_assert(sizeof(Q4) == sizeof(int4), "quantised segments are int4 by layout");
+    HIPCHK(e->render_walls.upload(walls));
+    HIPCHK(e->render_gates.upload(gates));
+    HIPCHK(e->render_trk.upload(trk));
+    HIPCHK(e->render_dirs.upload(dirs));
+    return PC_OK;
+}
+
 // Compile the tracks and classify the track_id layout on the host (track_tables.cpp), upload the tables, and let the device fill in what
 // it computes by the kernels' own arithmetic: the 1/den table, each track's reset observation and start_collides.
 static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8_t* track_id) {
@@ -698,7 +748,7 @@ static int env_create_impl(pc_env* e, const pc_track* const* tracks, const uint8
     HIPCHK(hipMemcpy(sc.data(), d_sc, e->n_tracks * sizeof(int), hipMemcpyDeviceToHost));
     for (int k = 0; k < e->n_tracks; ++k) e->hdr_host[k].start_collides = sc[k];
     HIPCHK(hipMemcpy(e->hdr, e->hdr_host.data(), e->n_tracks * sizeof(TrackHdr), hipMemcpyHostToDevice));
-    return PC_OK;
+    return render_prepare(e, tracks);
 }
 
 int pc_env_create(int device, int64_t n_envs, int num_rays_nominal, const pc_track* const* tracks, int n_tracks,
@@ -1082,6 +1132,72 @@ int pc_greedy(int device, const float* logits, int64_t N, int A, int64_t* action
 
 // the compute-unit count of a device, asked once per device (ids from 64 on: 256).  The one cache of the library: two threads that
 // race on an entry store the same value.
+// pc_render_*: W and H of a scale on the list, false otherwise
+static bool render_size(int scale, int* W, int* H) {
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 5 && scale != 8 && scale != 10) return false;
+    *W = 1280 / scale;
+    *H = 720 / scale;
+    return true;
+}
+static int render_half_width(int nominal, int scale) { return std::max(nominal, 3 * scale); }
+
+int pc_render_background(const pc_env* e, int scale, uint8_t* background, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    int W, H;
+    if (!e || !background) return PC_ERR_INVALID_ARG;
+    if (!render_size(scale, &W, &H)) return PC_ERR_INVALID_ARG;
+    if ((uintptr_t)background & 3) return PC_ERR_INVALID_ARG;
+    if (!e->render_err.empty()) {
+        g_hip_err = e->render_err;
+        return PC_ERR_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    const int64_t blocks = ((int64_t)e->n_tracks * W * H + 255) / 256;      // (at most 256 tracks x 3600 blocks)
+    hipLaunchKernelGGL(render_background_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, e->render_walls.p, e->render_gates.p,
+                       e->render_trk.p, e->n_tracks, scale, W, H, render_half_width(10, scale), render_half_width(10, scale), background);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_render_frames(const pc_env* e, const float* obs, int64_t obs_ld, const int32_t* next_gate, const uint8_t* track_id, int64_t M,
+                     int scale, const uint8_t* background, const uint8_t* palette, uint8_t* frames, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    static const uint8_t default_palette[PC_RENDER_COLORS][3] = {{24, 24, 28},  {58, 58, 66},   {235, 235, 235}, {60, 110, 60},      // render.py's COLORS, a road fill
+                                                                 {90, 230, 90}, {70, 110, 200}, {250, 210, 70},  {240, 80, 60}};     // and a hit-disc colour
+    int W, H;
+    if (!e || !obs || !background || !frames || M < 1 || obs_ld < e->D) return PC_ERR_INVALID_ARG;
+    if (!render_size(scale, &W, &H)) return PC_ERR_INVALID_ARG;
+    if (((uintptr_t)background & 3) || ((uintptr_t)frames & 3)) return PC_ERR_INVALID_ARG;
+    if (!e->render_err.empty()) {
+        g_hip_err = e->render_err;
+        return PC_ERR_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    RenderFrames a{};
+    a.obs = obs; a.obs_ld = obs_ld; a.next_gate = next_gate; a.track_id = track_id;
+    a.scale = scale; a.W = W; a.H = H;
+    a.tiles_x = (W + PC_RENDER_TILE_W - 1) / PC_RENDER_TILE_W;
+    a.tiles_y = (H + PC_RENDER_TILE_H - 1) / PC_RENDER_TILE_H;
+    a.R = e->R; a.n_tracks = e->n_tracks;
+    const int h_ray = render_half_width(2, scale), h_car = render_half_width(24, scale), h_gate = render_half_width(10, scale);
+    a.h2_ray = h_ray * h_ray; a.h2_hit = 20 * 20; a.h2_car = h_car * h_car; a.h2_gate = h_gate * h_gate;
+    a.h_max = std::max(h_car, 20);
+    a.dirs = e->render_dirs; a.gates = e->render_gates; a.trk = e->render_trk; a.bg = background; a.frames = frames;
+    const uint8_t (*pal)[3] = palette ? (const uint8_t (*)[3])palette : default_palette;
+    for (int k = 0; k < PC_RENDER_COLORS; ++k) a.pal.rgb[k] = (uint32_t)pal[k][0] | ((uint32_t)pal[k][1] << 8) | ((uint32_t)pal[k][2] << 16);
+    // a launch's grid stays below 2^32 threads: at most 2^24 - 1 workgroups, whole frames
+    const int64_t tiles = (int64_t)a.tiles_x * a.tiles_y, per_launch = ((1ll << 24) - 1) / tiles;
+    for (int64_t m0 = 0; m0 < M; m0 += per_launch) {
+        a.m0 = m0;
+        const int64_t n = std::min(per_launch, M - m0);
+        hipLaunchKernelGGL(render_frames_kernel, dim3((unsigned)(n * tiles)), dim3(256), 0, (hipStream_t)stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    return PC_OK;
+}
+
 static int device_cus(int device, int* out) {
     static std::atomic<int> n_cu[64];
     if (device < 0 || device >= 64) { *out = 256; return PC_OK; }

@@ -118,7 +118,11 @@ class VecCarEnv:
     """
 
     def __init__(self, n_envs, tracks, num_rays=12, reward_scaling=1.0, device="cuda", dtype="f32", track_id=None,
-                 record_episode_statistics=False):
+                 record_episode_statistics=False, render_mode=None):
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError(f"VecCarEnv: render_mode must be None or 'rgb_array', not {render_mode!r}")
+        self.render_mode = render_mode
+        self._renderers = {}
         self.device = torch.device("cuda", _device_index(device))
         self.num_envs = int(n_envs)
         self.num_rays = int(num_rays)
@@ -150,6 +154,7 @@ class VecCarEnv:
               "pc_env_create")
         self.close()
         self._h, self._tracks = h, tr
+        self._renderers = {}             # (their backgrounds are the old handle's tracks)
         self.obs_dim = lib.pc_env_obs_dim(h)
         self.act_dim = lib.pc_env_num_actions(h)
         # dtype f32: walls that float32 cannot order (crossing / touching non-neighbours, spikes, very short walls) are resolved by a
@@ -314,6 +319,25 @@ class VecCarEnv:
                                        self._ptr(obs, torch.float32, M * D, "obs"), self._ptr(collides, torch.uint8, M, "collides"),
                                        self._stream()), "pc_env_observe_poses")
         return obs
+
+    def render(self, envs=None, scale=2):
+        """gymnasium's rgb_array: frames of the CURRENT state of all envs, or of the listed ones in the listed order, uint8
+        [K, 720 / scale, 1280 / scale, 3] on the device (renderer.Renderer; one frame is frames[k]).  observe() into a scratch tensor, then
+        the rasteriser; the next gate of every env comes from the handle's own state.  The state is not modified."""
+        from .renderer import Renderer
+        r = self._renderers.get(scale)
+        if r is None:
+            r = self._renderers[scale] = Renderer(self, scale)
+        obs = self.observe()
+        ng = np.zeros(self.num_envs, np.int64)
+        check(lib.pc_env_get_state(self._h, None, None, None, None, None, None, ng.ctypes.data, None), "pc_env_get_state")
+        ng = torch.from_numpy(ng.astype(np.int32)).to(self.device)
+        tid = None if self._track_id is None else torch.from_numpy(self._track_id).to(self.device)
+        if envs is not None:
+            idx = torch.as_tensor(np.asarray(envs, np.int64).reshape(-1), device=self.device)
+            obs, ng = obs[idx].contiguous(), ng[idx].contiguous()
+            tid = None if tid is None else tid[idx].contiguous()
+        return r.frames(obs, next_gate=ng, track_id=tid)
 
     def last_step_kernel(self):
         """which kernel the last step() / step_many() launched: "K1" (generic per-step kernel), "K1f" (table-driven), "K1f-table" or "none"."""

@@ -24,16 +24,26 @@ track_maps=True: the evaluator owns a TrackMaps (track_maps.py), one plane set p
 in front of every window's pc_first_episodes with the state as it stands there -- the maps cover exactly the first episodes.  The
 persistent path has the observation rows already; the per-step path then keeps the window's rows (step t reads row t and writes row
 t + 1, the window's last step writes _next_obs) instead of stepping one row in place: the same launches on other addresses, the same
-state bits.  Off: not one launch or buffer is added."""
+state bits.  Off: not one launch or buffer is added.
+
+video_envs=K > 0: the evaluator keeps the observation rows, rewards and flags of envs 0 .. K - 1 for all 1000 steps ([1000, K, D]: a few
+hundred KB), copied out of each window's rows on both paths (the per-step path: one K x D copy in front of every step).  After run(),
+video_frames() renders every video_every_step-th step of each of those envs' FIRST episodes on the device (renderer.Renderer: a frame is
+a pure function of the observation row, the track and the next-gate index, which is the running count of the episode's gate steps --
+decoded from the rewards as pc_first_episodes decodes them -- modulo the track's gate count) and returns one contact sheet per frame
+time.  The copies read rows the windows have written and write the evaluator's own buffers: self.state holds the same bits with video
+on or off.  Off: not one launch or buffer is added."""
 import math
 import sys
 
+import numpy as np
 import torch
 
 from . import _capi
 from ._capi import PC_EPISODE_BUFFER, PC_EPISODE_STEPS, PC_FIRST_ROWS, PC_TIME_LIMIT, check, lib
 from .env import VecCarEnv
 from .model import PolicyRangeError
+from .renderer import Renderer, frame_size
 from .track_maps import TrackMaps
 
 EVAL_MEAN_KEYS = ("eval/episodic_return", "eval/episodic_return_min", "eval/episodic_return_max", "eval/episodic_length",
@@ -81,13 +91,20 @@ def evaluation_scalars(tot, reward_scaling, policy_range="fallback"):
 
 class Evaluator:
     def __init__(self, agent, tracks, n_envs=1024, num_rays=12, reward_scaling=0.1, device="cuda", dtype="f32", track_id=None,
-                 greedy=False, seed=0, chunk=250, rollout_kernel="auto", track_maps=False, track_maps_cell=8):
+                 greedy=False, seed=0, chunk=250, rollout_kernel="auto", track_maps=False, track_maps_cell=8, video_envs=0, video_scale=4,
+                 video_every_step=2):
         if int(n_envs) < 1:
             raise ValueError(f"Evaluator: n_envs must be >= 1, not {n_envs!r}")
         if int(chunk) < 1:
             raise ValueError(f"Evaluator: chunk must be >= 1, not {chunk!r}")
         if rollout_kernel not in ("auto", "mega", "steps"):
             raise ValueError(f"Evaluator: rollout_kernel must be 'auto', 'mega' or 'steps', not {rollout_kernel!r}")
+        if not 0 <= int(video_envs) <= int(n_envs):
+            raise ValueError(f"Evaluator: video_envs must be 0 .. n_envs = {int(n_envs)}, not {video_envs!r}")
+        if int(video_every_step) < 1:
+            raise ValueError(f"Evaluator: video_every_step must be >= 1, not {video_every_step!r}")
+        if int(video_envs) > 0:
+            frame_size(video_scale)         # (ValueError for a scale off the list, before anything is created)
         self.agent = agent
         self.envs = VecCarEnv(int(n_envs), tracks, num_rays=num_rays, reward_scaling=reward_scaling, device=device, dtype=dtype,
                               track_id=track_id)
@@ -116,6 +133,13 @@ class Evaluator:
             self.maps = TrackMaps(len(self.envs._tracks), track_maps_cell, self.device)
             if self.envs._track_id is not None:
                 self._map_track_id = torch.from_numpy(self.envs._track_id).to(self.device)
+        self.video_envs, self.video_scale, self.video_every_step = int(video_envs), video_scale, int(video_every_step)
+        self._vid = self._renderer = None
+        self._t0 = 0                    # the running window's first step (run() sets it)
+        if self.video_envs > 0:         # rows of envs 0 .. K - 1 in the step layout: row t = what the policy saw at step t, and step t's reward / flags
+            K = self.video_envs
+            self._vid = dict(obs=new(PC_TIME_LIMIT, K, D), rew=new(PC_TIME_LIMIT, K), term=new(PC_TIME_LIMIT, K), trunc=new(PC_TIME_LIMIT, K))
+            self._renderer = Renderer(self.envs, video_scale)
 
     def _alloc_mega(self):
         N, D, C = self.num_envs, self.envs.obs_dim, self.chunk
@@ -172,6 +196,13 @@ class Evaluator:
         check(rc, "pc_rollout_greedy" if self.greedy else "pc_rollout")
         if self.maps is not None:
             self._map(m["obs"], T, PC_EPISODE_BUFFER)
+        if self._vid is not None:       # Buffer layout -> step layout: step t's flags sit in row t + 1, the last step's in _next_*
+            v, K, t0 = self._vid, self.video_envs, self._t0
+            v["obs"][t0:t0 + T].copy_(m["obs"][:T, :K])
+            v["rew"][t0:t0 + T].copy_(self._rew[:T, :K])
+            for name, rows, last in (("term", self._term, self._next_term), ("trunc", self._trunc, self._next_trunc)):
+                v[name][t0:t0 + T - 1].copy_(rows[1:T, :K])
+                v[name][t0 + T - 1].copy_(last[:K])
         self._scan(T, PC_EPISODE_BUFFER)
         return True
 
@@ -188,6 +219,8 @@ class Evaluator:
         for t in range(T):
             if rows is not None:
                 obs = rows[t]
+            if self._vid is not None:
+                self._vid["obs"][self._t0 + t].copy_(obs[:self.video_envs])
             if h is not None and self.greedy:       # the argmax inside the policy step: two launches per step, no logits buffer
                 check(lib.pc_policy_act_greedy(h, obs.data_ptr(), N, self._image.data_ptr(), act.data_ptr(), None, self._logprob.data_ptr(),
                                                self._val.data_ptr(), None, st), "pc_policy_act_greedy")
@@ -205,6 +238,10 @@ class Evaluator:
             self.envs.step(act, out=(nxt, self._rew[t], self._term[t], self._trunc[t]))
         if rows is not None:
             self._map(rows, T, PC_EPISODE_STEPS)
+        if self._vid is not None:
+            v, K, t0 = self._vid, self.video_envs, self._t0
+            for name, src in (("rew", self._rew), ("term", self._term), ("trunc", self._trunc)):
+                v[name][t0:t0 + T].copy_(src[:T, :K])
         self._scan(T, PC_EPISODE_STEPS)
 
     @torch.no_grad()
@@ -221,6 +258,7 @@ class Evaluator:
         mega = self._mega
         for t0 in range(0, PC_TIME_LIMIT, self.chunk):
             T = min(self.chunk, PC_TIME_LIMIT - t0)
+            self._t0 = t0
             if mega and not self._window_mega(h, T, base + t0):
                 if t0 != 0:
                     raise RuntimeError("Evaluator: pc_rollout refused a window after it took the first one")
@@ -251,6 +289,52 @@ class Evaluator:
         """run + fetch: the eval/* dict of one evaluation (synchronises)."""
         self.run(index)
         return self.scalars(self.totals().tolist())
+
+    # ---- the video ---------------------------------------------------------------------------------------------------------------
+    def video_plan(self):
+        """What video_frames() renders, from the kept rewards and flags (synchronises): (steps [F, K] int64, next_gate [F, K] int32,
+        lengths [K]).  lengths[k] = the steps of env k's first episode; frame f shows env k at step min(f * video_every_step, the last
+        multiple of video_every_step below lengths[k]) -- a finished env holds its last frame -- and F covers the longest of the K
+        episodes.  next_gate of a step = the gate steps BEFORE it (k = rint(r / reward_scaling) in {1, 11, -2, 8}, pc_first_episodes'
+        decoding) modulo the gate count of the env's track."""
+        if self._vid is None:
+            raise RuntimeError("Evaluator(video_envs=K) keeps the rows of a video; this evaluator does not")
+        v, K, every = self._vid, self.video_envs, self.video_every_step
+        rew = v["rew"].cpu().numpy().astype(np.float64)
+        done = (v["term"].cpu().numpy() != 0) | (v["trunc"].cpu().numpy() != 0)
+        lengths = np.where(done.any(0), done.argmax(0) + 1, PC_TIME_LIMIT).astype(np.int64)
+        k = np.rint(rew / self.reward_scaling)
+        gate = np.isin(k, (1.0, 11.0, -2.0, 8.0))
+        before = np.cumsum(gate, axis=0) - gate                     # exclusive
+        tid = self.envs._track_id[:K].astype(np.int64) if self.envs._track_id is not None else np.zeros(K, np.int64)
+        n_gates = np.array([t.n_gates for t in self.envs._tracks], np.int64)[tid]
+        F = int((lengths.max() + every - 1) // every)
+        last = (lengths - 1) // every * every
+        steps = np.minimum(np.arange(F, dtype=np.int64)[:, None] * every, last[None, :])
+        ng = (before[steps, np.arange(K)[None, :]] % n_gates[None, :]).astype(np.int32)
+        return steps, ng, lengths
+
+    def video_frames(self, cols=None):
+        """The contact sheets of the last run(): host uint8 [F, rows * H, cols * W, 3], env k of frame f at row k // cols, column
+        k % cols (cols: default ceil(sqrt(K))).  Rendered in chunks of at most 256 frames."""
+        from .render import contact_sheet
+        steps, ng, _ = self.video_plan()
+        F, K = steps.shape
+        cols = int(cols) if cols is not None else int(math.ceil(math.sqrt(K)))
+        r = self._renderer
+        t_idx = torch.from_numpy(steps.reshape(-1)).to(self.device)
+        k_idx = torch.arange(K, device=self.device).repeat(F)
+        rows = self._vid["obs"][t_idx, k_idx]                      # [F * K, D]
+        gates = torch.from_numpy(ng.reshape(-1)).to(self.device)
+        tid = None
+        if self.envs._track_id is not None:
+            tid = torch.from_numpy(self.envs._track_id[:K].copy()).to(self.device).repeat(F)
+        out = np.empty((F * K, r.H, r.W, 3), np.uint8)
+        for a in range(0, F * K, 256):
+            b = min(a + 256, F * K)
+            out[a:b] = r.frames(rows[a:b], next_gate=gates[a:b], track_id=None if tid is None else tid[a:b]).cpu().numpy()
+        out = out.reshape(F, K, r.H, r.W, 3)
+        return np.stack([contact_sheet(out[f], cols) for f in range(F)])
 
     def close(self):
         self.envs.close()

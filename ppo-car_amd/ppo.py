@@ -135,11 +135,27 @@ class PPOConfig:
     eval_track_maps: bool = False          # with eval_every: the evaluator keeps maps of its first episodes (Evaluator(track_maps=True), cell size
                                            # track_maps_cell); train.py writes eval_track_maps_<epoch> after each evaluation
 
+    video_every: int = 0                   # train.py: K > 0 writes video_<epoch>.png every K-th epoch (the reference's log_video cadence is 10,
+                                           # train.py:23-50): an animated PNG of the first episodes of video_envs fresh envs under the updated
+                                           # policy, from an Evaluator as eval_every makes one (shared with it when both are on, else its own
+                                           # of video_envs envs, seeded by the epoch) and rendered on the device (Renderer).  Rank 0, after the
+                                           # epoch, outside any graph; training computes the same bits with it on or off
+    video_envs: int = 4                    # envs shown side by side
+    video_scale: int = 4                   # a frame is 1280 / scale x 720 / scale per env: 1, 2, 4, 5, 8 or 10
+
     def __post_init__(self):
         if self.eval_every < 0:
             raise ValueError(f"PPOConfig.eval_every must be >= 0 (0 = off), not {self.eval_every!r}")
         if self.eval_envs < 1:
             raise ValueError(f"PPOConfig.eval_envs must be >= 1, not {self.eval_envs!r}")
+        if self.video_every < 0:
+            raise ValueError(f"PPOConfig.video_every must be >= 0 (0 = off), not {self.video_every!r}")
+        if self.video_envs < 1:
+            raise ValueError(f"PPOConfig.video_envs must be >= 1, not {self.video_envs!r}")
+        if self.video_scale not in _capi.PC_RENDER_SCALES:
+            raise ValueError(f"PPOConfig.video_scale must be one of {_capi.PC_RENDER_SCALES}, not {self.video_scale!r}")
+        if self.video_every > 0 and self.eval_every > 0 and self.video_envs > self.eval_envs:
+            raise ValueError(f"PPOConfig.video_envs = {self.video_envs} exceeds eval_envs = {self.eval_envs}: the video shows envs of the evaluation")
         if self.track_maps_cell not in _capi.PC_MAP_CELLS:
             raise ValueError(f"PPOConfig.track_maps_cell must be one of {_capi.PC_MAP_CELLS}, not {self.track_maps_cell!r}")
         if self.track_maps_every < 0:
@@ -921,7 +937,17 @@ class Trainer:
                                        track_id=mixed_track_ids(ev_track, cfg.eval_envs, cfg.track_interleave),
                                        greedy=cfg.eval_greedy, seed=cfg.seed * 1000003 + 0x9E3779B9,
                                        rollout_kernel="steps" if cfg.rollout_kernel == "steps" else cfg.eval_rollout_kernel,
-                                       track_maps=cfg.eval_track_maps, track_maps_cell=cfg.track_maps_cell)
+                                       track_maps=cfg.eval_track_maps, track_maps_cell=cfg.track_maps_cell,
+                                       video_envs=cfg.video_envs if cfg.video_every > 0 else 0, video_scale=cfg.video_scale)
+        # video_every: the evaluation's envs 0 .. video_envs - 1 when eval_every is on too, else an evaluator of its own with video_envs envs
+        self.video_evaluator = self.evaluator if cfg.video_every > 0 else None
+        if cfg.video_every > 0 and self.evaluator is None and rank == 0 and self.device.type == "cuda":
+            self.video_evaluator = Evaluator(self.agent, cfg.track, n_envs=cfg.video_envs, num_rays=cfg.num_rays, reward_scaling=cfg.reward_scaling,
+                                             device=self.device, dtype=cfg.env_dtype,
+                                             track_id=mixed_track_ids(cfg.track, cfg.video_envs, cfg.track_interleave),
+                                             greedy=cfg.eval_greedy, seed=cfg.seed * 1000003 + 0x9E3779B9,
+                                             rollout_kernel="steps" if cfg.rollout_kernel == "steps" else cfg.eval_rollout_kernel,
+                                             video_envs=cfg.video_envs, video_scale=cfg.video_scale)
         # track_maps: rank 0 maps its own shard (the evaluator's rule: no collective); the handle's track ids are uploaded once
         self.track_maps = self._map_track_id = None
         if cfg.track_maps and rank == 0 and self.device.type == "cuda":
@@ -1208,6 +1234,18 @@ class Trainer:
         """The maps of the last evaluation's first episodes (eval_track_maps)."""
         return self.evaluator.maps.save(path_prefix, self.evaluator.envs._tracks)
 
+    def save_video(self, path, fps=30):
+        """video_every: an animated PNG of the updated policy's first episodes (Evaluator.video_frames; synchronises).  The shared
+        evaluator's run of this epoch is used where eval_every ran one; otherwise the evaluator runs here, at stream position = the epoch.
+        Returns the number of frames written."""
+        from .render import write_apng
+        ev = self.video_evaluator
+        if not (ev is self.evaluator and self.epoch % self.cfg.eval_every == 0):
+            ev.run(index=self.epoch)
+        frames = ev.video_frames()
+        write_apng(path, frames, fps=fps)
+        return len(frames)
+
     def load_state_dict(self, sd):
         L = self.learner
         if sd["fused"] != L.flat_adam:
@@ -1252,3 +1290,5 @@ class Trainer:
             self.envs.close()
             if self.evaluator is not None:
                 self.evaluator.close()
+            if self.video_evaluator is not None and self.video_evaluator is not self.evaluator:
+                self.video_evaluator.close()

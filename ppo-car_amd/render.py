@@ -90,3 +90,60 @@ def write_png(path, img):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+# ---- frames rendered on the device (renderer.py, pc_render_frames): the default palette, contact sheets, animated PNG ----------------
+# [PC_RENDER_COLORS][3] in the order of include/ppocar.h's PC_RENDER_* indices: grass, road, wall, gate, next gate, ray, hit disc, car
+# (COLORS plus a road fill and a hit-disc colour; the library's default when no palette is passed)
+DEFAULT_PALETTE = np.array([COLORS["background"], (58, 58, 66), COLORS["wall"], COLORS["gate"], COLORS["next_gate"], COLORS["ray"],
+                            (250, 210, 70), COLORS["car"]], np.uint8)
+
+
+def contact_sheet(frames, cols):
+    """frames uint8 [K, H, W, 3] -> one image of ceil(K / cols) rows x cols columns, frame k at row k // cols, column k % cols; cells
+    past K are black."""
+    frames = np.asarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3 or len(frames) < 1:
+        raise ValueError(f"contact_sheet: frames must be [K >= 1, H, W, 3], got {frames.shape}")
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError(f"contact_sheet: cols must be >= 1, not {cols}")
+    k, h, w, _ = frames.shape
+    rows = (k + cols - 1) // cols
+    sheet = np.zeros((rows * cols, h, w, 3), np.uint8)
+    sheet[:k] = frames
+    return sheet.reshape(rows, cols, h, w, 3).transpose(0, 2, 1, 3, 4).reshape(rows * h, cols * w, 3)
+
+
+def write_apng(path, frames, fps=30):
+    """Animated PNG (8-bit RGB, zlib only), frames uint8 [K, H, W, 3] played in a loop at `fps`: IHDR, acTL, then per frame an fcTL and
+    its image -- the first in IDAT (a viewer without APNG support shows it), the others in fdAT -- with one running sequence number over
+    the fcTL and fdAT chunks, then IEND."""
+    frames = np.asarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3 or len(frames) < 1:
+        raise ValueError(f"write_apng: frames must be [K >= 1, H, W, 3], got {frames.shape}")
+    fps = int(fps)
+    if not 1 <= fps <= 65535:
+        raise ValueError(f"write_apng: fps must be 1 .. 65535, not {fps}")
+    k, h, w, _ = frames.shape
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    out = [b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)), chunk(b"acTL", struct.pack(">II", k, 0))]
+    seq = 0
+    for i in range(k):
+        # fcTL: sequence, width, height, x / y offset, delay = 1 / fps s, dispose none, blend source
+        out.append(chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, w, h, 0, 0, 1, fps, 0, 0)))
+        seq += 1
+        rows = np.empty((h, 1 + 3 * w), np.uint8)
+        rows[:, 0] = 0                                          # filter type none
+        rows[:, 1:] = frames[i].reshape(h, 3 * w)
+        data = zlib.compress(rows.tobytes(), 6)
+        if i == 0:
+            out.append(chunk(b"IDAT", data))
+        else:
+            out.append(chunk(b"fdAT", struct.pack(">I", seq) + data))
+            seq += 1
+    out.append(chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(b"".join(out))

@@ -16,3 +16,4 @@ from .model import Agent, PolicyRangeError, layer_init  # noqa: E402,F401
 from .evaluation import Evaluator  # noqa: E402,F401
 from .track_maps import TrackMaps  # noqa: E402,F401
 from .landscape import PolicyLandscape  # noqa: E402,F401
+from .renderer import Renderer  # noqa: E402,F401

@@ -84,6 +84,11 @@ def parse_args(argv=None):
                    "landscape_<epoch>_landscape.npz + a PNG per track beside the checkpoints; 0 = never.  Training computes the same bits either way")
     p.add_argument("--landscape-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the landscape in pixels")
     p.add_argument("--landscape-speed", type=float, default=0.5, help="speed of the observed car as a fraction of max_speed, along its heading")
+    p.add_argument("--video-every", type=int, default=0, help="every this many epochs (rank 0; the reference logs a video every 10), write "
+                   "video_<epoch>.png beside the checkpoints: an animated PNG of the updated policy driving the first episodes of --video-envs "
+                   "fresh envs, rendered on the device (ppo_car_amd.Renderer); 0 = never.  Training computes the same bits either way")
+    p.add_argument("--video-envs", type=int, default=4, help="envs shown side by side in the video")
+    p.add_argument("--video-scale", type=int, default=4, choices=(1, 2, 4, 5, 8, 10), help="a video frame is 1280 / scale x 720 / scale per env")
     p.add_argument("--resume", default=None, help="trainer_<epoch>.pt written by an earlier run: continue it exactly")
     return p.parse_args(argv)
 
@@ -131,7 +136,8 @@ def main(argv=None):
                     large_minibatch=args.large_minibatch, eval_every=args.eval_every, eval_envs=args.eval_envs,
                     eval_greedy=args.eval_greedy, eval_track=args.eval_track, eval_rollout_kernel=args.eval_rollout_kernel,
                     track_maps=args.track_maps, track_maps_cell=args.track_maps_cell, track_maps_every=args.track_maps_every,
-                    eval_track_maps=args.eval_track_maps)
+                    eval_track_maps=args.eval_track_maps, video_every=args.video_every, video_envs=args.video_envs,
+                    video_scale=args.video_scale)
     trainer = Trainer(cfg, device=torch.device("cuda", local_rank), rank=rank, world_size=world)
     first_epoch = 1
     if args.resume:
@@ -177,6 +183,8 @@ def main(argv=None):
                     trainer.save_track_maps(os.path.join(ckpt_dir, f"track_maps_{epoch}"), clear=True)     # (this file: the epochs since the last one)
                 if args.eval_track_maps and trainer.evaluator is not None and epoch % args.eval_every == 0:
                     trainer.save_eval_track_maps(os.path.join(ckpt_dir, f"eval_track_maps_{epoch}"))
+                if trainer.video_evaluator is not None and epoch % args.video_every == 0:       # after the epoch, outside any graph
+                    trainer.save_video(os.path.join(ckpt_dir, f"video_{epoch}.png"))
                 if landscape is not None and epoch % args.landscape_every == 0:      # after the epoch, outside any graph, no random draw
                     landscape.compute().save(os.path.join(ckpt_dir, f"landscape_{epoch}"))
                 if epoch % 10 == 0:                                                                # train.py:280-283
