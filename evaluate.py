@@ -16,6 +16,9 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
     python evaluate.py --checkpoint ... --landscape out/eval [--landscape-cell 8] [--landscape-speed 0.5]
                                                                      # the policy landscape (ppo_car_amd.PolicyLandscape): value and greedy action
                                                                      # at every cell x 72 headings -> out/eval_landscape.npz and a PNG per track
+                      [--landscape-horizon 64] [--landscape-lookahead]
+                                                                     # ... plus how many steps the greedy policy survives from every pose
+                                                                     # (out/eval_survival_<track>.png) and the one-step look-ahead of all 9 actions
 """
 import argparse
 import json
@@ -45,6 +48,10 @@ def parse_args(argv=None):
                     "PREFIX_landscape_<track>.png, instead of running episodes")
     ap.add_argument("--landscape-cell", type=int, default=8, choices=(4, 5, 8, 10, 16, 20, 40, 80), help="cell size of the landscape in pixels")
     ap.add_argument("--landscape-speed", type=float, default=0.5, help="speed of the observed car as a fraction of max_speed, along its heading")
+    ap.add_argument("--landscape-horizon", type=int, default=0, metavar="H", help="--landscape: also drive the greedy policy H steps (1 .. 999) from every "
+                    "pose (PolicyLandscape.survival): `survived` in the .npz and PREFIX_survival_<track>.png; 0 = off")
+    ap.add_argument("--landscape-lookahead", action="store_true", help="--landscape: also step every pose once under each of the 9 actions "
+                    "(PolicyLandscape.lookahead): safe_actions, greedy_crashes and avoidable in the .npz")
     ap.add_argument("--video", default=None, metavar="FILE.png", help="--envs: write an animated PNG of the first episodes of envs 0 .. --video-envs - 1 "
                     "(every second step, rendered on the device from the evaluation's own observation rows)")
     ap.add_argument("--video-envs", type=int, default=4, help="envs shown side by side in the video")
@@ -155,10 +162,20 @@ def landscape(pc, args):
     agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     ls = pc.PolicyLandscape(agent, args.track, args.num_rays, cell_px=args.landscape_cell, speed=args.landscape_speed, device="cuda")
     try:
-        files = ls.compute().save(args.landscape)
+        ls.compute()
+        if args.landscape_horizon > 0:
+            ls.survival(args.landscape_horizon)
+        if args.landscape_lookahead:
+            ls.lookahead()
+        files = ls.save(args.landscape)
         best = ls.best_value()
         out = {"landscape": files, "cells": int(best.numel()), "drivable_cells": int((~best.isnan()).sum()),
                "poses": ls.n_tracks * ls.poses_per_track, "drivable_poses": int(ls.drivable.sum())}
+        if args.landscape_horizon > 0:      # cells with a heading from which the greedy policy drives the whole horizon
+            out["survival_horizon"] = args.landscape_horizon
+            out["cells_surviving"] = int((ls.survived.amax(1) >= args.landscape_horizon).sum())
+        if args.landscape_lookahead:
+            out["avoidable_poses"] = int(ls.avoidable.sum())
     finally:
         ls.close()
     print(json.dumps(out))

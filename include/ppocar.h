@@ -164,6 +164,37 @@ int pc_env_observe_poses(const pc_env* e, const double* px, const double* py, co
                          const int32_t* turns, const uint8_t* track_id, int64_t M, float* obs, uint8_t* collides, void* stream);
 int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream);
 
+/* ---- stepping without committing (opt-in: the entry points above are untouched): one CarEnv.step (car_env.py:693-760) of M states the
+ * caller names, on the handle's tracks.  One launch of one kernel (K20); no auto-reset; the handle's own env state is neither read
+ * nor written.  All arrays are DEVICE arrays of M entries, obs is [M][D]; M is independent of the handle's n_envs.
+ *   px, py, vx, vy        float64, IN / OUT: position in pixels and velocity in px per step
+ *   turns                 int32, IN / OUT: the heading, pc_env_observe_poses' rule; out: turns - 1 (a left turn), + 1 (right) or as it was
+ *   next_gate, time_step  int32, IN / OUT.  Only gate[next_gate] can fire; the last gate wraps next_gate to 0.  A next_gate outside
+ *                         0 .. G - 1 of the row's track: no gate can fire, the value is left as it is.
+ *     After the call the seven arrays hold the state CarEnv.step leaves -- also for a row that terminated or truncated: nothing is
+ *     reset, the position is the pose of the impact.  The update is IN PLACE: the arrays must not overlap one another.
+ *   actions     int64: CarEnv's 0 .. 8; anything else acts as 8 (no thrust, no turn)
+ *   track_id    uint8, or NULL = track 0            active   uint8, or NULL = every row
+ *   obs         [M][D] float32: the observation CarEnv.step itself returned (what pc_env_step writes to final_obs)
+ *   reward      float32, (float)(r * reward_scale) as pc_env_step scales and rounds it
+ *   terminated, truncated   uint8 0 / 1: a wall was hit; else time_step + 1 >= PC_TIME_LIMIT
+ *   gate        uint8 0 / 1 or NULL: a gate fired in this step (a lap closed iff gate and the new next_gate is 0)
+ * Rows that are not stepped: active[m] == 0 -- NOTHING of the row is written, in any array; a track_id the handle does not have --
+ * obs row zeros, reward 0, flags 0, the state untouched.
+ * Bits: on an F32 handle obs / reward / flags / the new state are pc_env_step's for the same state and action (the wall distances by
+ * the exhaustive float64 scan pc_env_observe_poses takes, so states on a wall or outside the track are fine).  On an F64 handle they
+ * are the reference's from any rotation `turns` names: the turn itself is the literal rot +- 5.0 of Car.move_car.  The new count
+ * turns +- 1 names the ONE-WAY rotation again, so a chained call after a turn back re-enters that row, which can lie a few ulps from
+ * rot +- 5.0 (on big_track 10 of 2000 turn-backs differ, on track 6, on oval64 4): as pc_env_observe_poses, a car that turned both
+ * ways can hold a rotation the count does not name.
+ * Checked before any device call, in this order: NULL handle; NULL px / py / vx / vy / turns / next_gate / time_step / actions / obs /
+ * reward / terminated / truncated; M < 1; reward_scale not finite: PC_ERR_INVALID_ARG; then as pc_env_observe_poses.  The call never
+ * synchronises. */
+int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, double* vy, int32_t* turns, int32_t* next_gate,
+                      int32_t* time_step, const uint8_t* track_id, const int64_t* actions, const uint8_t* active, int64_t M,
+                      double reward_scale, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* gate,
+                      void* stream);
+
 /* Per-handle launch options of pc_rollout (below).  Every choice gives bit-identical buffers; they exist so that the variant a
  * benchmark size takes can be checked at other batch sizes, and for A/B timing.
  *   PC_OPT_ROLLOUT_FORM  -1 (default) automatic: above 8192 envs independent waves of 32 envs, 256 envs per workgroup (128 up to

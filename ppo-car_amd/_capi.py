@@ -88,6 +88,7 @@ _sig = {
     "pc_env_info": (_i, [_vp, _vp, _vp, _vp]),
     "pc_env_observe_poses": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "pc_env_observe": (_i, [_vp, _vp, _vp, _vp]),
+    "pc_env_step_poses": (_i, [_vp] * 11 + [_i64, _d] + [_vp] * 6),
     "pc_build_ablate": (_i, []),
     "pc_env_get_state": (_i, [_vp] * 9),
     "pc_env_set_state": (_i, [_vp] * 9),

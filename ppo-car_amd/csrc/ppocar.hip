@@ -77,6 +77,7 @@
 #include "kernels/env_math.hpp"
 #include "kernels/env_step.hpp"
 #include "kernels/observe.hpp"
+#include "kernels/step_poses.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
@@ -534,24 +535,45 @@ static int greedy_small(int KS, int rpl, bool epw16, bool rden, RolloutLaunch& o
     return PC_OK;
 }
 
-// K17: lanes per pose -- enough to fill the device at small M (the rule of choose_geometry), never more than rays, one at large M; the
+// K17, K20: lanes per pose and the grid -- enough to fill the device at small M (the rule of choose_geometry), never more than rays, one at large M; the
 // handle's pc_env_set_lanes_per_env override applies (every choice writes the same bytes: a ray's value does not depend on its lane)
-template <typename T, bool STATE>
-static int observe_launch(const pc_env* e, ObservePoses q, float* obs, uint8_t* collides, hipStream_t st) {
+static int pose_geometry(const pc_env* e, const int64_t M, int& lg, unsigned& blocks) {
     int G = 1;
     if (e->lanes_override > 0) {
         while (2 * G <= e->lanes_override && 2 * G <= e->R) G <<= 1;
     } else {
-        while (2 * G <= e->R && G < 64 && (int64_t)G * q.M < 262144) G <<= 1;
+        while (2 * G <= e->R && G < 64 && (int64_t)G * M < 262144) G <<= 1;
     }
-    q.lg = 0;
-    while ((1 << q.lg) < G) ++q.lg;
+    lg = 0;
+    while ((1 << lg) < G) ++lg;
+    if (M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
+    const int64_t b = ((M << lg) + 255) / 256;
+    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
+    blocks = (unsigned)b;
+    return PC_OK;
+}
+
+template <typename T, bool STATE>
+static int observe_launch(const pc_env* e, ObservePoses q, float* obs, uint8_t* collides, hipStream_t st) {
+    unsigned blocks;
+    const int rc = pose_geometry(e, q.M, q.lg, blocks);
+    if (rc != PC_OK) return rc;
     q.n_tracks = e->n_tracks;
     q.turn_row = e->turn_row;
-    if (q.M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
-    const int64_t blocks = ((q.M << q.lg) + 255) / 256;
-    if (blocks > INT_MAX) return PC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((observe_kernel<T, STATE>), dim3((unsigned)blocks), dim3(256), 0, st, e->params<T>(), q, obs, collides);
+    hipLaunchKernelGGL((observe_kernel<T, STATE>), dim3(blocks), dim3(256), 0, st, e->params<T>(), q, obs, collides);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+// K20: K17's geometry (a row's bytes do not depend on the lanes it gets either)
+template <typename T>
+static int step_poses_launch(const pc_env* e, StepPoses q, float* obs, hipStream_t st) {
+    unsigned blocks;
+    const int rc = pose_geometry(e, q.M, q.lg, blocks);
+    if (rc != PC_OK) return rc;
+    q.n_tracks = e->n_tracks;
+    q.turn_row = e->turn_row;
+    hipLaunchKernelGGL((step_poses_kernel<T>), dim3(blocks), dim3(256), 0, st, e->params<T>(), q, obs);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }
@@ -885,6 +907,26 @@ int pc_env_observe_poses(const pc_env* e, const double* px, const double* py, co
     q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.track_id = track_id; q.M = M;
     return e->dtype == PC_DTYPE_F64 ? observe_launch<double, false>(e, q, obs, collides, (hipStream_t)stream)
                                     : observe_launch<float, false>(e, q, obs, collides, (hipStream_t)stream);
+}
+
+int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, double* vy, int32_t* turns, int32_t* next_gate,
+                      int32_t* time_step, const uint8_t* track_id, const int64_t* actions, const uint8_t* active, int64_t M,
+                      double reward_scale, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* gate,
+                      void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;      // (this and the refusals below come before the handle is looked at)
+    if (!px || !py || !vx || !vy || !turns || !next_gate || !time_step || !actions || !obs || !reward || !terminated || !truncated)
+        return PC_ERR_INVALID_ARG;
+    if (M < 1) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    StepPoses q{};
+    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.next_gate = next_gate; q.time_step = time_step;
+    q.track_id = track_id; q.actions = actions; q.active = active; q.M = M; q.reward_scale = reward_scale;
+    q.reward = reward; q.terminated = terminated; q.truncated = truncated; q.gate = gate;
+    return e->dtype == PC_DTYPE_F64 ? step_poses_launch<double>(e, q, obs, (hipStream_t)stream)
+                                    : step_poses_launch<float>(e, q, obs, (hipStream_t)stream);
 }
 
 int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {

@@ -1,6 +1,7 @@
 """VecCarEnv -- the gymnasium vector-env surface train.py drives (reference train.py:138-142,
 159-164,185,296), backed by the HIP env-step kernel through the C-ABI.  Tensors in, tensors out,
 everything stays on the GPU; no host synchronisation in step()."""
+import collections
 import ctypes as C
 import os
 
@@ -9,6 +10,9 @@ import torch
 
 from . import _capi
 from ._capi import check, lib
+
+# what VecCarEnv.step_poses returns (the stepped px, py, vx, vy, turns are the caller's own tensors, updated in place)
+StepPoses = collections.namedtuple("StepPoses", "obs reward terminated truncated gate next_gate time_step")
 
 
 class Track:
@@ -319,6 +323,37 @@ class VecCarEnv:
                                        self._ptr(obs, torch.float32, M * D, "obs"), self._ptr(collides, torch.uint8, M, "collides"),
                                        self._stream()), "pc_env_observe_poses")
         return obs
+
+    # ---- stepping without committing (pc_env_step_poses) ----------------------------------------------------------------------
+    def step_poses(self, px, py, vx, vy, turns, actions, next_gate=None, time_step=None, track_id=None, active=None, out=None):
+        """One CarEnv.step of M states the caller names, IN PLACE: px, py, vx, vy float64, turns int32 (observe_poses' heading rule),
+        next_gate / time_step int32 (None: a fresh zero tensor) are device tensors of M entries and hold the stepped state afterwards --
+        also where the step terminated or truncated: nothing is reset.  actions int64 (anything outside 0 .. 8 acts as 8), track_id
+        uint8 (default track 0), active uint8 (default every row; a row with 0 is not touched in any tensor).  out = (obs [M, D]
+        float32, reward [M] float32, terminated, truncated, gate [M] uint8) or None to allocate.  Returns StepPoses(obs, reward,
+        terminated, truncated, gate, next_gate, time_step).  A row whose track_id this env does not have gets zeros and keeps its
+        state.  The env's own state is neither read nor written; one launch, no synchronisation."""
+        if px.dim() != 1 or px.numel() < 1:
+            raise ValueError(f"step_poses: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
+        M, D = px.numel(), self.obs_dim
+        if next_gate is None:
+            next_gate = torch.zeros(M, dtype=torch.int32, device=self.device)
+        if time_step is None:
+            time_step = torch.zeros(M, dtype=torch.int32, device=self.device)
+        if out is None:
+            out = (self._new(M, D), self._new(M), self._new(M, dtype=torch.uint8), self._new(M, dtype=torch.uint8),
+                   self._new(M, dtype=torch.uint8))
+        obs, rew, term, trunc, gate = out
+        check(lib.pc_env_step_poses(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
+                                    self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
+                                    self._ptr(turns, torch.int32, M, "turns"), self._ptr(next_gate, torch.int32, M, "next_gate"),
+                                    self._ptr(time_step, torch.int32, M, "time_step"), self._ptr(track_id, torch.uint8, M, "track_id"),
+                                    self._ptr(actions, torch.int64, M, "actions"), self._ptr(active, torch.uint8, M, "active"), M,
+                                    self.reward_scaling, self._ptr(obs, torch.float32, M * D, "obs"),
+                                    self._ptr(rew, torch.float32, M, "reward"), self._ptr(term, torch.uint8, M, "terminated"),
+                                    self._ptr(trunc, torch.uint8, M, "truncated"), self._ptr(gate, torch.uint8, M, "gate"),
+                                    self._stream()), "pc_env_step_poses")
+        return StepPoses(obs, rew, term, trunc, gate, next_gate, time_step)
 
     def render(self, envs=None, scale=2):
         """gymnasium's rgb_array: frames of the CURRENT state of all envs, or of the listed ones in the listed order, uint8

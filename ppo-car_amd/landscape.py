@@ -6,7 +6,11 @@ policy step (pc_policy_act_greedy) runs on those observations.
 value [n_tracks, 72, GH, GW] float32 (the critic), action [.., 72, GH, GW] uint8 (the first argmax of the logits), drivable
 [.., 72, GH, GW] bool (Car.check_collision is false at the pose).  Heading index t means the track's start angle + 5 t degrees.
 compute() only enqueues (observe, act, two copies per chunk of at most 2^18 poses), draws no random number and writes nothing
-but its own tensors: a training run computes the same bits with or without it."""
+but its own tensors: a training run computes the same bits with or without it.
+
+survival(horizon) and lookahead() ask what happens from each pose, by stepping CLONES of the grid poses with K20 (pc_env_step_poses;
+nothing is committed to any env): survived [n_tracks, 72, GH, GW] int16, the steps the greedy policy completes without hitting a wall;
+safe_actions uint8, greedy_crashes and avoidable bool, the one-step look-ahead of all 9 actions.  They exist once their call has run."""
 import os
 
 import numpy as np
@@ -52,7 +56,7 @@ class PolicyLandscape:
     def __init__(self, agent, tracks, num_rays, cell_px=8, speed=0.5, dtype="f32", device="cuda", envs=None):
         """agent: ppo_car_amd.Agent (its act(obs, greedy=True)); tracks: one path / Track or a list; num_rays: Car's nominal ray
         count, which fixes the agent's input width.  The landscape owns a one-env handle, used for its track tables only.  (envs: an
-        object with observe_poses(), obs_dim and _tracks to use in its place -- the host tests' stand-in.)"""
+        object with observe_poses(), step_poses(), obs_dim and _tracks to use in its place -- the host tests' stand-in.)"""
         if cell_px not in PC_MAP_CELLS:
             raise ValueError(f"PolicyLandscape: cell_px must be one of {PC_MAP_CELLS}, not {cell_px!r}")
         if not 0.0 <= float(speed) <= 1.0:
@@ -84,6 +88,10 @@ class PolicyLandscape:
         self._act = torch.empty(n, dtype=torch.int64, device=self.device)
         self._logprob = torch.empty(n, dtype=torch.float32, device=self.device)
         self._collides = torch.empty(n, dtype=torch.uint8, device=self.device)
+        # survival() / lookahead(): created by the call that fills them
+        self.survived = self.survival_horizon = self.safe_actions = self.greedy_crashes = self.avoidable = None
+        self._computed = False
+        self._step_bufs = None
 
     def poses(self):
         """(px, py, vx, vy, turns, track_id): the device tensors compute() evaluates, [n_tracks * 72 * GH * GW] each."""
@@ -105,7 +113,90 @@ class PolicyLandscape:
                            repack=lo == 0)
             action[lo:hi].copy_(self._act[:n])
             torch.eq(collides, 0, out=drivable[lo:hi])
+        self._computed = True
         return self
+
+    # ---- what happens from each pose (K20, pc_env_step_poses: steps of clones of the grid poses; nothing is committed anywhere) -----
+    def _chunk_state(self, lo, hi):
+        """Fresh clones of the chunk's grid poses plus zero next_gate / time_step: the tensors step_poses() updates in place."""
+        z = torch.zeros(hi - lo, dtype=torch.int32, device=self.device)
+        return [t[lo:hi].clone() for t in (self._px, self._py, self._vx, self._vy, self._turns)] + [z, z.clone()]
+
+    def _step_out(self, n):
+        if self._step_bufs is None:
+            m = self._obs.shape[0]
+            u8 = lambda: torch.zeros(m, dtype=torch.uint8, device=self.device)
+            self._step_bufs = (torch.zeros(m, dtype=torch.float32, device=self.device), u8(), u8(), u8(),
+                               torch.zeros(m, dtype=torch.float32, device=self.device))
+        rew, term, trunc, gate, val = self._step_bufs
+        return (self._obs[:n], rew[:n], term[:n], trunc[:n], gate[:n]), val[:n]
+
+    def survival(self, horizon=64):
+        """Fill survived [n_tracks, 72, GH, GW] int16: how many steps the greedy policy completes from the pose without hitting a wall --
+        0 at a pose that is not drivable, `horizon` if it never crashes.  Per chunk of at most 2^18 poses: one pc_env_observe_poses, then
+        `horizon` times one pc_policy_act_greedy and one pc_env_step_poses on clones of the grid poses, active = still alive.  1 <= horizon
+        <= 999: the time limit cannot fire.  No random draw, no synchronisation; writes nothing but its own tensors.  Returns self."""
+        horizon = int(horizon)
+        if not 1 <= horizon <= 999:
+            raise ValueError(f"PolicyLandscape.survival: horizon must be in 1 .. 999, not {horizon!r}")
+        total = self.n_tracks * self.poses_per_track
+        if self.survived is None:
+            self.survived = torch.zeros((self.n_tracks, HEADINGS, *self.grid), dtype=torch.int16, device=self.device)
+        self.survived.zero_()
+        self.survival_horizon = horizon
+        survived = self.survived.view(-1)
+        for lo in range(0, total, CHUNK):
+            hi = min(lo + CHUNK, total)
+            n = hi - lo
+            px, py, vx, vy, turns, next_gate, time_step = self._chunk_state(lo, hi)
+            out, val = self._step_out(n)
+            obs, collides, tid = out[0], self._collides[:n], self._track_id[lo:hi]
+            self.envs.observe_poses(px, py, turns, vx=vx, vy=vy, track_id=tid, out=obs, collides=collides)
+            torch.eq(collides, 0, out=self.drivable.view(-1)[lo:hi])      # (what compute() writes there)
+            alive = (collides == 0).to(torch.uint8)
+            out[2].zero_()
+            for s in range(horizon):
+                self.agent.act(obs, out_action=self._act[:n], out_logprob=self._logprob[:n], out_value=val, greedy=True,
+                               repack=lo == 0 and s == 0)
+                self.envs.step_poses(px, py, vx, vy, turns, self._act[:n], next_gate=next_gate, time_step=time_step, track_id=tid,
+                                     active=alive, out=out)
+                alive &= out[2] == 0
+                survived[lo:hi] += alive
+        return self
+
+    def lookahead(self):
+        """One-step look-ahead from every grid pose, after compute() (RuntimeError otherwise): per chunk and for each of the 9 actions one
+        pc_env_step_poses on a clone of the chunk.  safe_actions uint8: how many actions' step does not terminate (0 where the pose is not
+        drivable); greedy_crashes bool: the pose is drivable and the step under compute()'s greedy action terminates; avoidable =
+        greedy_crashes & (safe_actions > 0).  No random draw, no synchronisation.  Returns self."""
+        if not self._computed:
+            raise RuntimeError("PolicyLandscape.lookahead() reads the action and drivable maps: call compute() first")
+        total = self.n_tracks * self.poses_per_track
+        shape = (self.n_tracks, HEADINGS, *self.grid)
+        self.safe_actions = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        self.greedy_crashes = torch.zeros(shape, dtype=torch.bool, device=self.device)
+        safe, crashes = self.safe_actions.view(-1), self.greedy_crashes.view(-1)
+        action, drivable = self.action.view(-1), self.drivable.view(-1)
+        for lo in range(0, total, CHUNK):
+            hi = min(lo + CHUNK, total)
+            n = hi - lo
+            out, _ = self._step_out(n)
+            ok = drivable[lo:hi]
+            active = ok.to(torch.uint8)
+            for a in range(9):
+                px, py, vx, vy, turns, next_gate, time_step = self._chunk_state(lo, hi)
+                self._act[:n].fill_(a)
+                self.envs.step_poses(px, py, vx, vy, turns, self._act[:n], next_gate=next_gate, time_step=time_step,
+                                     track_id=self._track_id[lo:hi], active=active, out=out)
+                term = out[2] != 0
+                safe[lo:hi] += (ok & ~term).to(torch.uint8)
+                crashes[lo:hi] |= ok & term & (action[lo:hi] == a)
+        self.avoidable = self.greedy_crashes & (self.safe_actions > 0)
+        return self
+
+    def best_survival(self, track=0):
+        """[GH, GW] float32: the most steps survived over the drivable headings; NaN where no heading is drivable."""
+        return best_value(self.survived[track].to(torch.float32), self.drivable[track])
 
     # ---- reductions over the headings (device tensors; no host synchronisation) -------------------------------------------------
     def best_value(self, track=0):
@@ -128,7 +219,9 @@ class PolicyLandscape:
     def save(self, path_prefix):
         """<path_prefix>_landscape.npz (value, action, drivable, best_value, best_heading, action_at_best, cell_px, speed, the track
         names) and one PNG per track, <path_prefix>_landscape_<track>.png: best_value on a linear ramp, walls and gates drawn over
-        it.  Synchronises (it fetches the tensors).  Returns the files written."""
+        it.  Whichever of survived (with survival_horizon), safe_actions, greedy_crashes, avoidable exist are added to the .npz, and
+        with survived one <path_prefix>_survival_<track>.png per track: the most steps survived over the drivable headings, linear
+        ramp.  Synchronises (it fetches the tensors).  Returns the files written."""
         from .render import heatmap, write_png
         names = [os.path.splitext(os.path.basename(os.fspath(t.path)))[0] if getattr(t, "path", None) is not None else f"track{k}"
                  for k, t in enumerate(self.tracks)]
@@ -137,14 +230,23 @@ class PolicyLandscape:
         os.makedirs(os.path.dirname(os.path.abspath(path_prefix)), exist_ok=True)
         best = np.stack([self.best_value(k).cpu().numpy() for k in range(self.n_tracks)])
         files = [f"{path_prefix}_landscape.npz"]
+        extra = {k: getattr(self, k).cpu().numpy() for k in ("survived", "safe_actions", "greedy_crashes", "avoidable")
+                 if getattr(self, k) is not None}      # (survival() / lookahead(): only what was computed)
+        if self.survived is not None:
+            extra["survival_horizon"] = np.int64(self.survival_horizon)
         np.savez_compressed(files[0], value=self.value.cpu().numpy(), action=self.action.cpu().numpy(), drivable=self.drivable.cpu().numpy(),
                             best_value=best, best_heading=np.stack([self.best_heading(k).cpu().numpy() for k in range(self.n_tracks)]),
                             action_at_best=np.stack([self.action_at_best(k).cpu().numpy() for k in range(self.n_tracks)]),
-                            cell_px=np.int64(self.cell_px), speed=np.float64(self.speed), tracks=np.array(names))
+                            cell_px=np.int64(self.cell_px), speed=np.float64(self.speed), tracks=np.array(names), **extra)
         for k, t in enumerate(self.tracks):
             walls, gates = t.geometry()
             files.append(f"{path_prefix}_landscape_{names[k]}.png")
             write_png(files[-1], heatmap(best[k].astype(np.float64), walls, gates, log=False))
+        if self.survived is not None:      # the most steps survived over the drivable headings, on a linear ramp
+            for k, t in enumerate(self.tracks):
+                walls, gates = t.geometry()
+                files.append(f"{path_prefix}_survival_{names[k]}.png")
+                write_png(files[-1], heatmap(self.best_survival(k).cpu().numpy().astype(np.float64), walls, gates, log=False))
         return files
 
     def close(self):
