@@ -10,6 +10,9 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
     python evaluate.py --checkpoint ... --envs 4096 --greedy --rollout-kernel mega     # ... the greedy windows as persistent launches
     python evaluate.py --checkpoint ... --envs 4096 --maps out/eval                    # ... plus telemetry maps of those first episodes:
                                                                      # out/eval.npz and a PNG per plane (visits, mean speed, crashes)
+    python evaluate.py --checkpoint ... --envs 4096 --greedy --shield 2                # ... shielded: an action that cannot avoid a crash within
+                                                                     # 2 steps is replaced by the best one that can (per-step path);
+                                                                     # adds eval/shield_interventions and eval/shield_doomed
     python evaluate.py --checkpoint ... --envs 64 --video out.png [--video-envs 4] [--video-scale 4] [--video-fps 30]
                                                                      # ... plus an animated PNG of envs 0 .. 3 driving their first episodes,
                                                                      # rendered on the device (ppo_car_amd.Renderer), side by side
@@ -41,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--rollout-kernel", choices=("auto", "mega", "steps"), default="auto",
                     help="--envs: how the Evaluator steps -- 'mega' = persistent launches (pc_rollout; with --greedy pc_rollout_greedy), 'steps' = "
                     "the per-step kernels, 'auto' = mega for sampled evaluations, steps for greedy ones")
+    ap.add_argument("--shield", type=int, default=0, metavar="D", help="--envs: shielded evaluation (Evaluator(shield_depth=D), D = 1 .. 4): an action "
+                    "that cannot avoid a crash within D steps is replaced by the safe action with the highest logit; per-step path only; 0 = off")
     ap.add_argument("--maps", default=None, metavar="PREFIX", help="--envs: write telemetry maps of the first episodes (ppo_car_amd.TrackMaps: "
                     "visits, mean speed and crashes per cell) to PREFIX.npz and PREFIX_<track>_<plane>.png")
     ap.add_argument("--landscape", default=None, metavar="PREFIX", help="write the policy landscape (ppo_car_amd.PolicyLandscape: the critic's value, "
@@ -59,6 +64,8 @@ def parse_args(argv=None):
     ap.add_argument("--video-fps", type=int, default=30)
     args = ap.parse_args(argv)
     check_video_args(args)
+    if args.shield and args.rollout_kernel == "mega":
+        raise ValueError("--shield masks the action between the policy step and the env step: --rollout-kernel must be 'auto' or 'steps', not 'mega'")
     return args
 
 
@@ -138,7 +145,7 @@ def batched(pc, args):
     agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     ev = pc.Evaluator(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda", greedy=args.greedy,
                       seed=args.seed, rollout_kernel=args.rollout_kernel, track_maps=args.maps is not None,
-                      video_envs=args.video_envs if args.video is not None else 0, video_scale=args.video_scale)
+                      video_envs=args.video_envs if args.video is not None else 0, video_scale=args.video_scale, shield_depth=args.shield)
     try:
         out = ev.evaluate()
         out["path"] = ev.last_path

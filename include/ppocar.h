@@ -195,6 +195,35 @@ int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, doubl
                       double reward_scale, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* gate,
                       void* stream);
 
+/* ---- safe-action masks (opt-in: the entry points above are untouched): which of the 9 actions can still avoid a crash within `depth`
+ * steps.  With step = CarEnv.step without auto-reset, as pc_env_step_poses defines it:
+ *   safe(s, a, 1) = not terminated(step(s, a))
+ *   safe(s, a, d) = not terminated(s' = step(s, a)) and (truncated(s') or exists a' in 0 .. 8: safe(s', a', d - 1))
+ * A branch that reaches the time limit without a crash ended its episode alive: safe.  `terminated` is pc_env_step_poses': one of
+ * check_collision's rays r in range(0, n, n // 4) at the NEW pose is shorter than 10 px, or the track's start pose collides.  Gates
+ * and rewards play no part.  One launch of one kernel (K21): an exhaustive search over the action sequences, one lane per (state, first
+ * action), the state in registers, no observation computed or stored; a level ends at its first surviving action.
+ * pc_env_safe_actions: M states, all DEVICE arrays of M entries, read only; M is independent of the handle's n_envs and the handle's
+ * env state is not read.
+ *   px, py, vx, vy   float64 position and velocity         turns   int32, pc_env_observe_poses' heading rule
+ *   time_step        int32, or NULL = 0                     track_id   uint8, or NULL = track 0        active   uint8, or NULL = every row
+ *   depth            1 .. PC_SAFE_MAX_DEPTH: the worst case is 9 + 81 + 729 + 6561 crash tests per state at depth 4
+ *   safe             [M][9] uint8, 0 / 1.  active[m] == 0: the row's 9 bytes are not written.  A track_id the handle does not have: 9 zeros.
+ * pc_env_safe_actions_state: the same for the handle's CURRENT state, safe [n_envs][9]; the heading is taken from the state as
+ *   pc_env_step takes it.  The state is not modified.
+ * Bits: on an F32 handle safe[m][a] is what enumerating all action sequences with chained pc_env_step_poses calls on that handle gives
+ * (the turn count is periodic there, so the chain is exact).  On an F64 handle it is that enumeration on the reference from the rotation
+ * `turns` names: inside the search the heading moves as Car.move_car moves it, the literal rot +- 5.0, and never re-enters the one-way
+ * row of a count -- exact also where chained pc_env_step_poses calls are a few ulps off after a turn back (the note above).
+ * Checked before any device call, in this order: NULL handle; NULL px / py / vx / vy / turns / safe; M < 1; depth outside 1 ..
+ * PC_SAFE_MAX_DEPTH (pc_env_safe_actions_state: NULL handle or safe; depth): PC_ERR_INVALID_ARG; then as pc_env_observe_poses.
+ * Neither call synchronises. */
+#define PC_SAFE_MAX_DEPTH 4
+int pc_env_safe_actions(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy,
+                        const int32_t* turns, const int32_t* time_step, const uint8_t* track_id, const uint8_t* active, int64_t M,
+                        int depth, uint8_t* safe, void* stream);
+int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream);
+
 /* Per-handle launch options of pc_rollout (below).  Every choice gives bit-identical buffers; they exist so that the variant a
  * benchmark size takes can be checked at other batch sizes, and for A/B timing.
  *   PC_OPT_ROLLOUT_FORM  -1 (default) automatic: above 8192 envs independent waves of 32 envs, 256 envs per workgroup (128 up to

@@ -78,6 +78,7 @@
 #include "kernels/env_step.hpp"
 #include "kernels/observe.hpp"
 #include "kernels/step_poses.hpp"
+#include "kernels/safe_actions.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
@@ -578,6 +579,25 @@ static int step_poses_launch(const pc_env* e, StepPoses q, float* obs, hipStream
     return PC_OK;
 }
 
+// K21: one lane per (state, first action), 256 threads; a kernel per search depth (the recursion below the first action is compile-time)
+template <typename T>
+static int safe_actions_launch(const pc_env* e, SafeActions q, const int depth, uint8_t* safe, hipStream_t st) {
+    if (q.M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
+    const int64_t b = (q.M * 9 + 255) / 256;
+    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
+    q.n_tracks = e->n_tracks;
+    q.turn_row = e->turn_row;
+    const dim3 grid((unsigned)b), block(256);
+    switch (depth) {
+        case 1: hipLaunchKernelGGL((safe_actions_kernel<T, 1>), grid, block, 0, st, e->params<T>(), q, safe); break;
+        case 2: hipLaunchKernelGGL((safe_actions_kernel<T, 2>), grid, block, 0, st, e->params<T>(), q, safe); break;
+        case 3: hipLaunchKernelGGL((safe_actions_kernel<T, 3>), grid, block, 0, st, e->params<T>(), q, safe); break;
+        default: hipLaunchKernelGGL((safe_actions_kernel<T, 4>), grid, block, 0, st, e->params<T>(), q, safe); break;
+    }
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
 extern "C" {
 
 const char* pc_strerror(int code) {
@@ -927,6 +947,34 @@ int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, doubl
     q.reward = reward; q.terminated = terminated; q.truncated = truncated; q.gate = gate;
     return e->dtype == PC_DTYPE_F64 ? step_poses_launch<double>(e, q, obs, (hipStream_t)stream)
                                     : step_poses_launch<float>(e, q, obs, (hipStream_t)stream);
+}
+
+int pc_env_safe_actions(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
+                        const int32_t* time_step, const uint8_t* track_id, const uint8_t* active, int64_t M, int depth, uint8_t* safe,
+                        void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;      // (this and the refusals below come before the handle is looked at)
+    if (!px || !py || !vx || !vy || !turns || !safe) return PC_ERR_INVALID_ARG;
+    if (M < 1) return PC_ERR_INVALID_ARG;
+    if (depth < 1 || depth > PC_SAFE_MAX_DEPTH) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    SafeActions q{};
+    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.time_step = time_step; q.track_id = track_id; q.active = active; q.M = M;
+    return e->dtype == PC_DTYPE_F64 ? safe_actions_launch<double>(e, q, depth, safe, (hipStream_t)stream)
+                                    : safe_actions_launch<float>(e, q, depth, safe, (hipStream_t)stream);
+}
+
+int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e || !safe) return PC_ERR_INVALID_ARG;
+    if (depth < 1 || depth > PC_SAFE_MAX_DEPTH) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    SafeActions q{};      // (px == nullptr: the kernel reads the handle's own state)
+    q.M = e->N;
+    return e->dtype == PC_DTYPE_F64 ? safe_actions_launch<double>(e, q, depth, safe, (hipStream_t)stream)
+                                    : safe_actions_launch<float>(e, q, depth, safe, (hipStream_t)stream);
 }
 
 int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {

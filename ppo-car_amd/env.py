@@ -355,6 +355,34 @@ class VecCarEnv:
                                     self._stream()), "pc_env_step_poses")
         return StepPoses(obs, rew, term, trunc, gate, next_gate, time_step)
 
+    # ---- safe-action masks (pc_env_safe_actions, pc_env_safe_actions_state) ----------------------------------------------------
+    def safe_actions(self, px, py, vx, vy, turns, depth=1, time_step=None, track_id=None, active=None, out=None):
+        """Which of the 9 actions can still avoid a crash within `depth` steps (1 .. 4) from each of M states: bool [M, 9].  safe[m, a] is
+        true iff the step under a does not terminate and -- for depth > 1 -- it truncates or some action is safe at depth - 1 from where
+        it leads (a branch that reaches the time limit alive is safe).  px, py, vx, vy float64, turns int32 (observe_poses' heading rule),
+        time_step int32 (default 0), track_id uint8 (default track 0), active uint8 (default every row; a row with 0 keeps its 9 bytes):
+        device tensors of M entries, all read only.  out: a [M, 9] uint8 tensor to fill (the returned bool tensor is a view of it).  A row
+        whose track_id this env does not have is all false.  The env state is neither read nor written; one launch, no synchronisation."""
+        if px.dim() != 1 or px.numel() < 1:
+            raise ValueError(f"safe_actions: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
+        M = px.numel()
+        safe = out if out is not None else self._new(M, 9, dtype=torch.uint8)
+        check(lib.pc_env_safe_actions(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
+                                      self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
+                                      self._ptr(turns, torch.int32, M, "turns"), self._ptr(time_step, torch.int32, M, "time_step"),
+                                      self._ptr(track_id, torch.uint8, M, "track_id"), self._ptr(active, torch.uint8, M, "active"), M,
+                                      int(depth), self._ptr(safe, torch.uint8, M * 9, "out"), self._stream()), "pc_env_safe_actions")
+        return safe.view(torch.bool)
+
+    def action_masks(self, depth=1, out=None):
+        """The admissible actions of every env's CURRENT state (sb3-contrib's name for it): bool [n_envs, 9], safe_actions() of the state
+        as step() holds it.  out: a [n_envs, 9] uint8 tensor to fill.  The state is not modified; one launch, no synchronisation."""
+        N = self.num_envs
+        safe = out if out is not None else self._new(N, 9, dtype=torch.uint8)
+        check(lib.pc_env_safe_actions_state(self._h, int(depth), self._ptr(safe, torch.uint8, N * 9, "out"), self._stream()),
+              "pc_env_safe_actions_state")
+        return safe.view(torch.bool)
+
     def render(self, envs=None, scale=2):
         """gymnasium's rgb_array: frames of the CURRENT state of all envs, or of the listed ones in the listed order, uint8
         [K, 720 / scale, 1280 / scale, 3] on the device (renderer.Renderer; one frame is frames[k]).  observe() into a scratch tensor, then

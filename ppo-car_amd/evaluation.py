@@ -32,7 +32,17 @@ video_frames() renders every video_every_step-th step of each of those envs' FIR
 a pure function of the observation row, the track and the next-gate index, which is the running count of the episode's gate steps --
 decoded from the rewards as pc_first_episodes decodes them -- modulo the track's gate count) and returns one contact sheet per frame
 time.  The copies read rows the windows have written and write the evaluator's own buffers: self.state holds the same bits with video
-on or off.  Off: not one launch or buffer is added."""
+on or off.  Off: not one launch or buffer is added.
+
+shield_depth=d > 0 (per-step path only; with rollout_kernel="mega" a ValueError): a shielded evaluation.  Every step takes the policy's
+own action as without a shield (the draw or the argmax: the random stream is the same), asks pc_env_safe_actions_state which actions
+can still avoid a crash within d steps, and where the chosen action cannot while another can, replaces it by the safe action with the
+highest logit (pc_greedy of the logits with the unsafe entries at -FLT_MAX: the lowest index on ties).  A row with no safe action keeps
+its action.  Over the steps of the first episodes (an env counts until the step that closes its first episode, that step included:
+pc_first_episodes' rule) it counts the steps, the replaced steps and the steps with no safe action: shield_totals(), and
+eval/shield_interventions and eval/shield_doomed in evaluate()'s dict.  A crash of an unshielded policy that the shield prevents was
+tactical; what is left with the shield on was decided more than d steps ahead.  Off (0, the default): not one launch, tensor or key
+is added."""
 import math
 import sys
 
@@ -55,6 +65,8 @@ EVAL_KEYS = ("eval/episodes",) + EVAL_MEAN_KEYS
 #   8 sum of row 5 (the lap times' sum)   9 min of row 6 (best lap)   10 envs that lapped   11 sum of their first laps
 #   12 the range status of the evaluator's weight image (include/ppocar.h PC_POLICY_RANGE_*; 0 = inside the arithmetic's domain)
 EVAL_TOTALS = 13
+SHIELD_KEYS = ("eval/shield_interventions", "eval/shield_doomed")
+# Evaluator.shield_totals(): float64 [3] = steps of the first episodes, those whose action the shield replaced, those with no safe action
 _warned_range = False
 
 
@@ -92,7 +104,12 @@ def evaluation_scalars(tot, reward_scaling, policy_range="fallback"):
 class Evaluator:
     def __init__(self, agent, tracks, n_envs=1024, num_rays=12, reward_scaling=0.1, device="cuda", dtype="f32", track_id=None,
                  greedy=False, seed=0, chunk=250, rollout_kernel="auto", track_maps=False, track_maps_cell=8, video_envs=0, video_scale=4,
-                 video_every_step=2):
+                 video_every_step=2, shield_depth=0):
+        if not 0 <= int(shield_depth) <= _capi.PC_SAFE_MAX_DEPTH:
+            raise ValueError(f"Evaluator: shield_depth must be 0 (off) .. {_capi.PC_SAFE_MAX_DEPTH}, not {shield_depth!r}")
+        if int(shield_depth) > 0 and rollout_kernel == "mega":
+            raise ValueError("Evaluator: shield_depth > 0 masks the action between the policy step and the env step, which only the "
+                             "per-step path has: rollout_kernel must be 'auto' or 'steps', not 'mega'")
         if int(n_envs) < 1:
             raise ValueError(f"Evaluator: n_envs must be >= 1, not {n_envs!r}")
         if int(chunk) < 1:
@@ -119,6 +136,13 @@ class Evaluator:
         self._state0 = self.state.clone()
         self._fused = bool(agent._std_mlp()) and agent.policy_form() is not None
         self._mega = self._fused and (rollout_kernel == "mega" if self.greedy else rollout_kernel != "steps")
+        self.shield_depth = int(shield_depth)
+        self._shield = None
+        if self.shield_depth > 0:       # the per-step path, whatever "auto" would take
+            self._mega = False
+            self._shield = dict(logits=new(N, A), masked=new(N, A), mask=new(N, 9, dtype=torch.uint8), act=new(N, dtype=torch.int64),
+                                running=torch.ones(N, dtype=torch.bool, device=self.device),
+                                counts=torch.zeros(3, dtype=torch.float64, device=self.device))
         self._image = self._image_handle = None
         self._range = torch.zeros(1, dtype=torch.int32, device=self.device)
         # rows of one window (both layouts), the observation / flags the next step starts from, and the per-step outputs
@@ -221,21 +245,28 @@ class Evaluator:
                 obs = rows[t]
             if self._vid is not None:
                 self._vid["obs"][self._t0 + t].copy_(obs[:self.video_envs])
+            lg_out = self._shield["logits"].data_ptr() if self._shield is not None else None
             if h is not None and self.greedy:       # the argmax inside the policy step: two launches per step, no logits buffer
                 check(lib.pc_policy_act_greedy(h, obs.data_ptr(), N, self._image.data_ptr(), act.data_ptr(), None, self._logprob.data_ptr(),
-                                               self._val.data_ptr(), None, st), "pc_policy_act_greedy")
+                                               self._val.data_ptr(), lg_out, st), "pc_policy_act_greedy")
             elif h is not None:
                 check(lib.pc_policy_act(h, obs.data_ptr(), N, self._image.data_ptr(), self.seed, offset + t, None, act.data_ptr(), None,
-                                        self._logprob.data_ptr(), self._val.data_ptr(), None, st), "pc_policy_act")
+                                        self._logprob.data_ptr(), self._val.data_ptr(), lg_out, st), "pc_policy_act")
             else:           # outside the fused kernel's menu: torch's GEMMs in front of the draw
                 lg = self.agent.actor(obs).contiguous()
+                if self._shield is not None:
+                    self._shield["logits"].copy_(lg)
                 if self.greedy:
                     check(lib.pc_greedy(di, lg.data_ptr(), N, self.envs.act_dim, act.data_ptr(), None, None, st), "pc_greedy")
                 else:
                     check(lib.pc_sample(di, lg.data_ptr(), N, lg.shape[1], self.seed, offset + t, act.data_ptr(), self._logprob.data_ptr(),
                                         None, st), "pc_sample")
+            if self._shield is not None:
+                self._shield_step(act)
             nxt = obs if rows is None else (rows[t + 1] if t + 1 < T else self._next_obs)
             self.envs.step(act, out=(nxt, self._rew[t], self._term[t], self._trunc[t]))
+            if self._shield is not None:    # an env counts up to and including the step that closes its first episode
+                self._shield["running"] &= (self._term[t] == 0) & (self._trunc[t] == 0)
         if rows is not None:
             self._map(rows, T, PC_EPISODE_STEPS)
         if self._vid is not None:
@@ -243,6 +274,19 @@ class Evaluator:
             for name, src in (("rew", self._rew), ("term", self._term), ("trunc", self._trunc)):
                 v[name][t0:t0 + T].copy_(src[:T, :K])
         self._scan(T, PC_EPISODE_STEPS)
+
+    def _shield_step(self, act):
+        """The shield between the policy step and the env step: `act` (the policy's own choice) is replaced, in place, where its byte of
+        the state's safe-action mask is 0 and the row has a safe action, by the first maximum of the logits over the safe actions."""
+        sh, N, A = self._shield, self.num_envs, self.envs.act_dim
+        mask = self.envs.action_masks(self.shield_depth, out=sh["mask"])              # bool [N, 9]
+        torch.where(mask[:, :A], sh["logits"], torch.full_like(sh["logits"], torch.finfo(torch.float32).min), out=sh["masked"])
+        check(lib.pc_greedy(self.device.index, sh["masked"].data_ptr(), N, A, sh["act"].data_ptr(), None, None, self._stream()), "pc_greedy")
+        doomed = ~mask.any(1)
+        replace = ~mask.gather(1, act.unsqueeze(1)).squeeze(1) & ~doomed
+        torch.where(replace, sh["act"], act, out=act)
+        run = sh["running"]
+        sh["counts"] += torch.stack([run.sum(), (run & replace).sum(), (run & doomed).sum()]).to(torch.float64)
 
     @torch.no_grad()
     def run(self, index=0):
@@ -252,6 +296,9 @@ class Evaluator:
         self._next_term.zero_()
         self._next_trunc.zero_()
         self.state.copy_(self._state0)
+        if self._shield is not None:
+            self._shield["running"].fill_(True)
+            self._shield["counts"].zero_()
         if self.maps is not None:
             self.maps.clear()
         base = int(index) * PC_TIME_LIMIT
@@ -280,15 +327,29 @@ class Evaluator:
                           one((s[4] == float(_capi.PC_FIRST_TERMINATED)).sum()), one(s[5].sum()), one(s[6].min()), one(lapped.sum()),
                           one(torch.where(lapped, s[7], torch.zeros_like(s[7])).sum()), one(self._range)])
 
-    def scalars(self, host_totals, reward_scaling=None):
-        """Host totals (totals() fetched: tolist()) -> the eval/* dict; see evaluation_scalars."""
-        return evaluation_scalars(host_totals, self.reward_scaling if reward_scaling is None else reward_scaling,
-                                  getattr(self.agent, "policy_range", "fallback"))
+    def shield_totals(self):
+        """Evaluator(shield_depth=d): float64 [3] on the device, no host synchronisation -- the steps of the first episodes of the last
+        run(), those whose action the shield replaced, those with no safe action."""
+        if self._shield is None:
+            raise RuntimeError("Evaluator(shield_depth=d) counts the shield's interventions; this evaluator has no shield")
+        return self._shield["counts"]
+
+    def scalars(self, host_totals, reward_scaling=None, host_shield_totals=None):
+        """Host totals (totals() fetched: tolist()) -> the eval/* dict; see evaluation_scalars.  host_shield_totals (shield_totals()
+        fetched) adds eval/shield_interventions and eval/shield_doomed: the shares of the first episodes' steps."""
+        out = evaluation_scalars(host_totals, self.reward_scaling if reward_scaling is None else reward_scaling,
+                                 getattr(self.agent, "policy_range", "fallback"))
+        if host_shield_totals is not None:
+            steps, replaced, doomed = host_shield_totals
+            out["eval/shield_interventions"], out["eval/shield_doomed"] = replaced / steps, doomed / steps
+        return out
 
     def evaluate(self, index=0):
         """run + fetch: the eval/* dict of one evaluation (synchronises)."""
         self.run(index)
-        return self.scalars(self.totals().tolist())
+        if self._shield is None:
+            return self.scalars(self.totals().tolist())
+        return self.scalars(self.totals().tolist(), host_shield_totals=self.shield_totals().tolist())
 
     # ---- the video ---------------------------------------------------------------------------------------------------------------
     def video_plan(self):

@@ -10,7 +10,11 @@ but its own tensors: a training run computes the same bits with or without it.
 
 survival(horizon) and lookahead() ask what happens from each pose, by stepping CLONES of the grid poses with K20 (pc_env_step_poses;
 nothing is committed to any env): survived [n_tracks, 72, GH, GW] int16, the steps the greedy policy completes without hitting a wall;
-safe_actions uint8, greedy_crashes and avoidable bool, the one-step look-ahead of all 9 actions.  They exist once their call has run."""
+safe_actions uint8, greedy_crashes and avoidable bool, the one-step look-ahead of all 9 actions.  They exist once their call has run.
+
+viability(depth) asks the same of all 9 actions `depth` steps deep with ONE K21 launch per chunk (pc_env_safe_actions: the exhaustive
+search on the device, no observation computed): viable [n_tracks, 72, GH, GW] uint16, bit a set iff action a can still avoid a crash
+within `depth` steps; doomed and avoidable_late bool."""
 import os
 
 import numpy as np
@@ -90,6 +94,7 @@ class PolicyLandscape:
         self._collides = torch.empty(n, dtype=torch.uint8, device=self.device)
         # survival() / lookahead(): created by the call that fills them
         self.survived = self.survival_horizon = self.safe_actions = self.greedy_crashes = self.avoidable = None
+        self.viable = self.viability_depth = self.doomed = self.avoidable_late = None      # viability()
         self._computed = False
         self._step_bufs = None
 
@@ -194,6 +199,39 @@ class PolicyLandscape:
         self.avoidable = self.greedy_crashes & (self.safe_actions > 0)
         return self
 
+    def viability(self, depth=3):
+        """Which actions can still avoid a crash within `depth` steps (1 .. 4) from every grid pose, after compute() (RuntimeError
+        otherwise): per chunk one pc_env_safe_actions with active = drivable.  viable uint16: bit a is set iff action a is safe at `depth`
+        (VecCarEnv.safe_actions), 0 where the pose is not drivable; doomed bool: drivable and no bit set; avoidable_late bool: compute()'s
+        greedy action has its bit clear and some other bit is set.  At depth 1 the bit count is lookahead()'s safe_actions and
+        avoidable_late its avoidable.  No random draw, no synchronisation; writes nothing but its own tensors.  Returns self."""
+        if not self._computed:
+            raise RuntimeError("PolicyLandscape.viability() reads the action and drivable maps: call compute() first")
+        total = self.n_tracks * self.poses_per_track
+        shape = (self.n_tracks, HEADINGS, *self.grid)
+        self.viable = torch.zeros(shape, dtype=torch.uint16, device=self.device)
+        self.viability_depth = int(depth)
+        viable, drivable = self.viable.view(-1), self.drivable.view(-1)
+        bit = torch.arange(9, dtype=torch.int32, device=self.device)
+        safe = torch.zeros(min(CHUNK, total), 9, dtype=torch.uint8, device=self.device)
+        for lo in range(0, total, CHUNK):
+            hi = min(lo + CHUNK, total)
+            ok = drivable[lo:hi]
+            self.envs.safe_actions(self._px[lo:hi], self._py[lo:hi], self._vx[lo:hi], self._vy[lo:hi], self._turns[lo:hi], depth=int(depth),
+                                   track_id=self._track_id[lo:hi], active=ok.to(torch.uint8), out=safe[:hi - lo])
+            bits = (safe[:hi - lo].to(torch.int32) << bit).sum(1, dtype=torch.int32)
+            viable[lo:hi].copy_(torch.where(ok, bits, torch.zeros_like(bits)))      # (an inactive row's bytes were not written)
+        v = self.viable.to(torch.int32)
+        self.doomed = self.drivable & (v == 0)
+        self.avoidable_late = (((v >> self.action.to(torch.int32)) & 1) == 0) & (v != 0)
+        return self
+
+    def viable_count(self, track=0):
+        """[GH, GW] float32: the most safe actions over the drivable headings; NaN where no heading is drivable."""
+        v = self.viable[track].to(torch.int32)
+        count = ((v.unsqueeze(-1) >> torch.arange(9, dtype=torch.int32, device=self.device)) & 1).sum(-1)
+        return best_value(count.to(torch.float32), self.drivable[track])
+
     def best_survival(self, track=0):
         """[GH, GW] float32: the most steps survived over the drivable headings; NaN where no heading is drivable."""
         return best_value(self.survived[track].to(torch.float32), self.drivable[track])
@@ -230,10 +268,13 @@ class PolicyLandscape:
         os.makedirs(os.path.dirname(os.path.abspath(path_prefix)), exist_ok=True)
         best = np.stack([self.best_value(k).cpu().numpy() for k in range(self.n_tracks)])
         files = [f"{path_prefix}_landscape.npz"]
-        extra = {k: getattr(self, k).cpu().numpy() for k in ("survived", "safe_actions", "greedy_crashes", "avoidable")
-                 if getattr(self, k) is not None}      # (survival() / lookahead(): only what was computed)
+        extra = {k: getattr(self, k).cpu().numpy() for k in ("survived", "safe_actions", "greedy_crashes", "avoidable", "viable", "doomed",
+                                                             "avoidable_late")
+                 if getattr(self, k) is not None}      # (survival() / lookahead() / viability(): only what was computed)
         if self.survived is not None:
             extra["survival_horizon"] = np.int64(self.survival_horizon)
+        if self.viable is not None:
+            extra["viability_depth"] = np.int64(self.viability_depth)
         np.savez_compressed(files[0], value=self.value.cpu().numpy(), action=self.action.cpu().numpy(), drivable=self.drivable.cpu().numpy(),
                             best_value=best, best_heading=np.stack([self.best_heading(k).cpu().numpy() for k in range(self.n_tracks)]),
                             action_at_best=np.stack([self.action_at_best(k).cpu().numpy() for k in range(self.n_tracks)]),
@@ -247,6 +288,11 @@ class PolicyLandscape:
                 walls, gates = t.geometry()
                 files.append(f"{path_prefix}_survival_{names[k]}.png")
                 write_png(files[-1], heatmap(self.best_survival(k).cpu().numpy().astype(np.float64), walls, gates, log=False))
+        if self.viable is not None:        # how many actions are still safe, the most over the drivable headings, on a linear ramp
+            for k, t in enumerate(self.tracks):
+                walls, gates = t.geometry()
+                files.append(f"{path_prefix}_viability_{names[k]}.png")
+                write_png(files[-1], heatmap(self.viable_count(k).cpu().numpy().astype(np.float64), walls, gates, log=False))
         return files
 
     def close(self):
