@@ -22,6 +22,10 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
                       [--landscape-horizon 64] [--landscape-lookahead]
                                                                      # ... plus how many steps the greedy policy survives from every pose
                                                                      # (out/eval_survival_<track>.png) and the one-step look-ahead of all 9 actions
+    python evaluate.py --planner shooting --plan-horizon 16 --plan-candidates 256 --envs 1024 [--track ...]
+                                                                     # no checkpoint: the first episodes of 1024 envs under a random-shooting
+                                                                     # planner on the env's own model (ppo_car_amd.PlannerEvaluator), the same
+                                                                     # eval/* scalars: the model-based baseline a policy's figures stand beside
 """
 import argparse
 import json
@@ -31,7 +35,8 @@ import torch
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--checkpoint", required=True, help="agent state_dict as train.py saves it (checkpoint_<n>.dat / model.dat)")
+    ap.add_argument("--checkpoint", default=None, help="agent state_dict as train.py saves it (checkpoint_<n>.dat / model.dat); required "
+                    "unless --planner is given")
     ap.add_argument("--track", default="tracks/big_track.json")
     ap.add_argument("--num-rays", type=int, default=12)
     ap.add_argument("--episodes", type=int, default=5)
@@ -62,7 +67,20 @@ def parse_args(argv=None):
     ap.add_argument("--video-envs", type=int, default=4, help="envs shown side by side in the video")
     ap.add_argument("--video-scale", type=int, default=4, help="a video frame is 1280 / scale x 720 / scale per env: 1, 2, 4, 5, 8 or 10")
     ap.add_argument("--video-fps", type=int, default=30)
+    # the planner's options appear in the namespace only when given: without --planner it is the namespace it always was
+    ap.add_argument("--planner", choices=("shooting",), default=argparse.SUPPRESS, help="--envs: evaluate a random-shooting planner on the env's own "
+                    "model (ppo_car_amd.PlannerEvaluator) instead of a checkpoint's policy")
+    ap.add_argument("--plan-horizon", type=int, default=argparse.SUPPRESS, metavar="H", help="--planner: steps per candidate sequence (default 16)")
+    ap.add_argument("--plan-candidates", type=int, default=argparse.SUPPRESS, metavar="K", help="--planner: sequences scored per env and step, "
+                    "the first 9 hold one action each (default 256)")
     args = ap.parse_args(argv)
+    if not hasattr(args, "planner"):
+        if args.checkpoint is None:
+            ap.error("the following arguments are required: --checkpoint")
+        if hasattr(args, "plan_horizon") or hasattr(args, "plan_candidates"):
+            ap.error("--plan-horizon / --plan-candidates belong to --planner")
+    elif args.envs is None:
+        raise ValueError("--planner evaluates the batched first episodes: pass --envs N")
     check_video_args(args)
     if args.shield and args.rollout_kernel == "mega":
         raise ValueError("--shield masks the action between the policy step and the env step: --rollout-kernel must be 'auto' or 'steps', not 'mega'")
@@ -88,6 +106,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py needs the GPU: the env has no CPU path")
     import ppo_car_amd as pc
+    if hasattr(args, "planner"):
+        return planned(pc, args)
     if args.landscape is not None:
         return landscape(pc, args)
     if args.envs is not None:
@@ -156,6 +176,20 @@ def batched(pc, args):
             frames = ev.video_frames()
             write_apng(args.video, frames, fps=args.video_fps)
             out["video"] = {"file": args.video, "frames": int(frames.shape[0]), "height": int(frames.shape[1]), "width": int(frames.shape[2])}
+    finally:
+        ev.close()
+    print(json.dumps(out))
+    return out
+
+
+def planned(pc, args):
+    """--planner shooting --envs N: N first episodes under the shooting planner, the eval/* scalars of batched()."""
+    ev = pc.PlannerEvaluator(args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda",
+                             horizon=getattr(args, "plan_horizon", 16), candidates=getattr(args, "plan_candidates", 256), seed=args.seed)
+    try:
+        out = ev.evaluate()
+        out["path"] = ev.last_path
+        out["planner"] = {"kind": args.planner, "horizon": ev.planner.horizon, "candidates": ev.planner.candidates}
     finally:
         ev.close()
     print(json.dumps(out))

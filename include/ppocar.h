@@ -224,6 +224,52 @@ int pc_env_safe_actions(const pc_env* e, const double* px, const double* py, con
                         int depth, uint8_t* safe, void* stream);
 int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream);
 
+/* ---- scoring action sequences (opt-in: the entry points above are untouched): what each of K action sequences of H steps earns from
+ * each of M states.  With step = CarEnv.step without auto-reset, as pc_env_step_poses defines it, sequence k of state m is stepped
+ * until it terminates, truncates or has taken its H steps; an ended sequence takes no further step and adds nothing.  One launch of
+ * one kernel (K22), one lane per (state, sequence), the state in registers, no observation computed or stored; where a best_* array
+ * is asked for, a second small launch in the same call picks each state's best sequence.
+ * pc_env_rollout_sequences: M states, all DEVICE arrays of M entries, read only; M is independent of the handle's n_envs and the
+ * handle's env state is not read.
+ *   px, py, vx, vy   float64 position and velocity         turns   int32, pc_env_observe_poses' heading rule
+ *   next_gate        int32, or NULL = 0 (pc_env_step_poses' rule: only gate[next_gate] can fire)         time_step   int32, or NULL = 0
+ *   track_id         uint8, or NULL = track 0               active  uint8, or NULL = every row
+ *   actions          uint8, TIME-MAJOR [H][K]: entry (t, k) is the action of sequence k in its step t; anything outside 0 .. 8 acts
+ *                    as 8.  actions_state_stride == 0: one table shared by all states; == H * K (bytes): M tables, state m's at
+ *                    actions + m * H * K.  Any other stride is refused.
+ *   K                1 .. PC_SEQ_MAX_CANDIDATES             H   1 .. PC_TIME_LIMIT
+ *   reward_scale     each step's reward is (float)(r * reward_scale), as pc_env_step scales and rounds it
+ * Per (state, sequence), [M][K]:
+ *   ret      float64: the sum, in step order, of those float32 rewards widened to double
+ *   steps    int32: steps taken, 1 .. H
+ *   status   uint8: PC_FIRST_RUNNING, PC_FIRST_TERMINATED or PC_FIRST_TRUNCATED after the last step taken (a crash in the step in which
+ *            the time limit falls due: TERMINATED)
+ *   gates, laps   int32 or NULL: gates fired; gates that wrapped next_gate to 0
+ * Per state, [M], each or NULL:
+ *   best_k        int32: the LOWEST k whose ret is the row's maximum, compared as float64
+ *   best_action   int64: that sequence's first action after the 0 .. 8 mapping, ready for pc_env_step
+ *   best_ret      float64: ret[m][best_k]
+ * Rows that are not rolled out: active[m] == 0 -- NOTHING of the row is written, in any output array; a track_id the handle does not
+ * have -- ret 0, steps 0, status PC_FIRST_RUNNING, gates and laps 0, best_k 0, best_action 8, best_ret 0.
+ * pc_env_rollout_sequences_state: the same for the handle's CURRENT state (M = n_envs, its own next_gate, time_step and track ids);
+ *   the heading is taken from the state as pc_env_step takes it.  The state is not modified.
+ * Bits: on an F32 handle every output is what H chained pc_env_step_poses calls on that handle give for the replicated rows (the turn
+ * count is periodic there, so the chain is exact).  On an F64 handle it is the reference's from the rotation `turns` names: inside a
+ * sequence the heading moves as Car.move_car moves it, the literal rot +- 5.0, as in pc_env_safe_actions.
+ * Checked before any device call, in this order: NULL handle; NULL px / py / vx / vy / turns / actions / ret / steps / status
+ * (pc_env_rollout_sequences_state: actions / ret / steps / status); M < 1; K outside 1 .. PC_SEQ_MAX_CANDIDATES; H outside 1 ..
+ * PC_TIME_LIMIT; a stride other than 0 or H * K; reward_scale not finite: PC_ERR_INVALID_ARG; then as pc_env_observe_poses.  Neither
+ * call synchronises. */
+#define PC_SEQ_MAX_CANDIDATES 4096
+int pc_env_rollout_sequences(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy,
+                             const int32_t* turns, const int32_t* next_gate, const int32_t* time_step, const uint8_t* track_id,
+                             const uint8_t* active, int64_t M, const uint8_t* actions, int64_t actions_state_stride, int K, int H,
+                             double reward_scale, double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps,
+                             int32_t* best_k, int64_t* best_action, double* best_ret, void* stream);
+int pc_env_rollout_sequences_state(pc_env* e, const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale,
+                                   double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k,
+                                   int64_t* best_action, double* best_ret, void* stream);
+
 /* Per-handle launch options of pc_rollout (below).  Every choice gives bit-identical buffers; they exist so that the variant a
  * benchmark size takes can be checked at other batch sizes, and for A/B timing.
  *   PC_OPT_ROLLOUT_FORM  -1 (default) automatic: above 8192 envs independent waves of 32 envs, 256 envs per workgroup (128 up to

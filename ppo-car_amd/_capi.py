@@ -28,6 +28,7 @@ PC_RENDER_SCALES = (1, 2, 4, 5, 8, 10)            # ... frames are 1280 / scale 
 PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppocar.h)
 PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_SAFE_MAX_DEPTH = 4    # pc_env_safe_actions: the deepest search (include/ppocar.h)
+PC_SEQ_MAX_CANDIDATES = 4096     # pc_env_rollout_sequences: the most sequences per state (include/ppocar.h)
 PC_TIME_LIMIT = 1000    # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
 PC_OPT_ROLLOUT_FORM, PC_OPT_ROLLOUT_EPW, PC_OPT_ROLLOUT_FAST = 1, 2, 3
 PC_KERNEL_NAMES = {0: "none", 1: "K9", 2: "K9s", 3: "K9-literal", 4: "K9d-filter", 5: "K9s-literal", 6: "K9d-selector", 7: "K9m", 8: "K9m-literal"}     # pc_env_last_rollout_kernel
@@ -92,6 +93,8 @@ _sig = {
     "pc_env_step_poses": (_i, [_vp] * 11 + [_i64, _d] + [_vp] * 6),
     "pc_env_safe_actions": (_i, [_vp] * 9 + [_i64, _i, _vp, _vp]),
     "pc_env_safe_actions_state": (_i, [_vp, _i, _vp, _vp]),
+    "pc_env_rollout_sequences": (_i, [_vp] * 10 + [_i64, _vp, _i64, _i, _i, _d] + [_vp] * 9),
+    "pc_env_rollout_sequences_state": (_i, [_vp, _vp, _i64, _i, _i, _d] + [_vp] * 9),
     "pc_build_ablate": (_i, []),
     "pc_env_get_state": (_i, [_vp] * 9),
     "pc_env_set_state": (_i, [_vp] * 9),

@@ -79,6 +79,7 @@
 #include "kernels/observe.hpp"
 #include "kernels/step_poses.hpp"
 #include "kernels/safe_actions.hpp"
+#include "kernels/sequences.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
@@ -598,6 +599,24 @@ static int safe_actions_launch(const pc_env* e, SafeActions q, const int depth, 
     return PC_OK;
 }
 
+// K22: one lane per (state, sequence), 256 threads; then, where a best_* array is asked for, a wave per state over what the first stored
+template <typename T>
+static int sequences_launch(const pc_env* e, Sequences q, hipStream_t st) {
+    if (q.M > (INT64_MAX >> 13)) return PC_ERR_UNSUPPORTED;
+    const int64_t b = (q.M * q.K + 255) / 256;
+    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
+    q.n_tracks = e->n_tracks;
+    q.turn_row = e->turn_row;
+    const EnvParams<T> p = e->params<T>();
+    hipLaunchKernelGGL((sequences_kernel<T>), dim3((unsigned)b), dim3(256), 0, st, p, q);
+    HIPCHK(hipGetLastError());
+    if (q.best_k || q.best_action || q.best_ret) {
+        hipLaunchKernelGGL(sequences_best_kernel, dim3((unsigned)((q.M + 3) / 4)), dim3(256), 0, st, q, p.track_id);
+        HIPCHK(hipGetLastError());
+    }
+    return PC_OK;
+}
+
 extern "C" {
 
 const char* pc_strerror(int code) {
@@ -975,6 +994,50 @@ int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream)
     q.M = e->N;
     return e->dtype == PC_DTYPE_F64 ? safe_actions_launch<double>(e, q, depth, safe, (hipStream_t)stream)
                                     : safe_actions_launch<float>(e, q, depth, safe, (hipStream_t)stream);
+}
+
+int pc_env_rollout_sequences(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
+                             const int32_t* next_gate, const int32_t* time_step, const uint8_t* track_id, const uint8_t* active, int64_t M,
+                             const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale, double* ret,
+                             int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k, int64_t* best_action,
+                             double* best_ret, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;      // (this and the refusals below come before the handle is looked at)
+    if (!px || !py || !vx || !vy || !turns || !actions || !ret || !steps || !status) return PC_ERR_INVALID_ARG;
+    if (M < 1) return PC_ERR_INVALID_ARG;
+    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
+    if (H < 1 || H > PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
+    if (actions_state_stride != 0 && actions_state_stride != (int64_t)H * K) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    Sequences q{};
+    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.next_gate = next_gate; q.time_step = time_step;
+    q.track_id = track_id; q.active = active; q.M = M;
+    q.actions = actions; q.state_stride = actions_state_stride; q.K = K; q.H = H; q.reward_scale = reward_scale;
+    q.ret = ret; q.steps = steps; q.status = status; q.gates = gates; q.laps = laps;
+    q.best_k = best_k; q.best_action = best_action; q.best_ret = best_ret;
+    return e->dtype == PC_DTYPE_F64 ? sequences_launch<double>(e, q, (hipStream_t)stream) : sequences_launch<float>(e, q, (hipStream_t)stream);
+}
+
+int pc_env_rollout_sequences_state(pc_env* e, const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale,
+                                   double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k,
+                                   int64_t* best_action, double* best_ret, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;
+    if (!actions || !ret || !steps || !status) return PC_ERR_INVALID_ARG;
+    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
+    if (H < 1 || H > PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
+    if (actions_state_stride != 0 && actions_state_stride != (int64_t)H * K) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    Sequences q{};      // (px == nullptr: the kernel reads the handle's own state)
+    q.M = e->N;
+    q.actions = actions; q.state_stride = actions_state_stride; q.K = K; q.H = H; q.reward_scale = reward_scale;
+    q.ret = ret; q.steps = steps; q.status = status; q.gates = gates; q.laps = laps;
+    q.best_k = best_k; q.best_action = best_action; q.best_ret = best_ret;
+    return e->dtype == PC_DTYPE_F64 ? sequences_launch<double>(e, q, (hipStream_t)stream) : sequences_launch<float>(e, q, (hipStream_t)stream);
 }
 
 int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {

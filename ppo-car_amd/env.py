@@ -383,6 +383,57 @@ class VecCarEnv:
               "pc_env_safe_actions_state")
         return safe.view(torch.bool)
 
+    # ---- scoring action sequences (pc_env_rollout_sequences, pc_env_rollout_sequences_state) -----------------------------------------
+    _SEQ_OUT = (("ret", torch.float64, True), ("steps", torch.int32, True), ("status", torch.uint8, True), ("gates", torch.int32, True),
+                ("laps", torch.int32, True), ("best_k", torch.int32, False), ("best_action", torch.int64, False),
+                ("best_ret", torch.float64, False))
+
+    def _sequence_args(self, what, M, actions, reward_scale, out):
+        """(the call's trailing arguments from `actions` on, the dict to return)"""
+        if actions.dtype != torch.uint8 or actions.dim() not in (2, 3) or (actions.dim() == 3 and actions.shape[0] != M):
+            raise ValueError(f"{what}: actions must be a uint8 tensor [H, K] (shared) or [{M}, H, K] (per state), got "
+                             f"{tuple(actions.shape)} {actions.dtype}")
+        H, K = actions.shape[-2:]
+        stride = H * K if actions.dim() == 3 else 0
+        res = {}
+        for name, dtype, per_lane in self._SEQ_OUT:
+            if out is None or (name not in out and name in ("ret", "steps", "status")):
+                res[name] = self._new(M, K, dtype=dtype) if per_lane else self._new(M, dtype=dtype)
+            else:
+                res[name] = out.get(name)      # an `out` without an optional key: that array is not asked for
+        ptrs = [self._ptr(res[name], dtype, M * K if per_lane else M, name) for name, dtype, per_lane in self._SEQ_OUT]
+        scale = self.reward_scaling if reward_scale is None else float(reward_scale)
+        args = [self._ptr(actions, torch.uint8, actions.numel(), "actions"), stride, K, H, scale] + ptrs + [self._stream()]
+        return args, {k: v for k, v in res.items() if v is not None}
+
+    def rollout_sequences(self, px, py, vx, vy, turns, actions, next_gate=None, time_step=None, track_id=None, active=None,
+                          reward_scale=None, out=None):
+        """What each of K action sequences of H steps earns from each of M states (step = step_poses' step; a sequence that terminated
+        or truncated takes no further step).  px, py, vx, vy float64, turns int32 (observe_poses' heading rule), next_gate / time_step
+        int32 (default 0), track_id uint8 (default track 0), active uint8 (default every row; a row with 0 is not written in any
+        output): device tensors of M entries, all read only.  actions: uint8, time-major [H, K] shared by all states or [M, H, K], one
+        table per state; anything outside 0 .. 8 acts as 8.  reward_scale: default the env's reward_scaling.  Returns a dict of device
+        tensors: ret float64, steps int32, status uint8 (_capi.PC_FIRST_*), gates, laps int32, each [M, K]; best_k int32 (the lowest k
+        of the row's maximum), best_action int64 (its first action), best_ret float64, each [M].  out: a dict of tensors to fill; with
+        `out` given, an optional key it lacks (gates, laps, best_*) is not computed.  A row whose track_id this env does not have gets
+        zeros (best_action 8).  The env state is neither read nor written; no synchronisation."""
+        if px.dim() != 1 or px.numel() < 1:
+            raise ValueError(f"rollout_sequences: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
+        M = px.numel()
+        args, res = self._sequence_args("rollout_sequences", M, actions, reward_scale, out)
+        check(lib.pc_env_rollout_sequences(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
+                                           self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
+                                           self._ptr(turns, torch.int32, M, "turns"), self._ptr(next_gate, torch.int32, M, "next_gate"),
+                                           self._ptr(time_step, torch.int32, M, "time_step"), self._ptr(track_id, torch.uint8, M, "track_id"),
+                                           self._ptr(active, torch.uint8, M, "active"), M, *args), "pc_env_rollout_sequences")
+        return res
+
+    def score_sequences(self, actions, reward_scale=None, out=None):
+        """rollout_sequences() of every env's CURRENT state, as step() holds it (M = n_envs).  The state is not modified."""
+        args, res = self._sequence_args("score_sequences", self.num_envs, actions, reward_scale, out)
+        check(lib.pc_env_rollout_sequences_state(self._h, *args), "pc_env_rollout_sequences_state")
+        return res
+
     def render(self, envs=None, scale=2):
         """gymnasium's rgb_array: frames of the CURRENT state of all envs, or of the listed ones in the listed order, uint8
         [K, 720 / scale, 1280 / scale, 3] on the device (renderer.Renderer; one frame is frames[k]).  observe() into a scratch tensor, then

@@ -77,6 +77,17 @@ def new_state(n_envs, device):
     return s
 
 
+def state_totals(s, range_status):
+    """A pc_first_episodes state [8, N] reduced over envs in a fixed order, with the range-status word (int32 [1]) as entry 12: float64
+    [EVAL_TOTALS] on the state's device, no host synchronisation."""
+    lapped = torch.isfinite(s[7])
+    one = lambda x: x.reshape(1).to(torch.float64)
+    return torch.cat([torch.full((1,), float(s.shape[1]), dtype=torch.float64, device=s.device), one(s[0].sum()),
+                      one(s[0].min()), one(s[0].max()), one(s[1].sum()), one(s[2].sum()), one(s[3].sum()),
+                      one((s[4] == float(_capi.PC_FIRST_TERMINATED)).sum()), one(s[5].sum()), one(s[6].min()), one(lapped.sum()),
+                      one(torch.where(lapped, s[7], torch.zeros_like(s[7])).sum()), one(range_status)])
+
+
 def evaluation_scalars(tot, reward_scaling, policy_range="fallback"):
     """Host totals (Evaluator.totals(), tolist()) -> the eval/* keys.  Returns are unscaled.  The lap keys are None where no env lapped.
     A non-zero range status (the weights left the fp16 x 2 policy arithmetic's domain: the episodes were not this policy's) makes every
@@ -319,13 +330,7 @@ class Evaluator:
     def totals(self):
         """The state reduced over envs in a fixed order, and the weight image's range status: float64 [EVAL_TOTALS] on the device, no
         host synchronisation."""
-        s = self.state
-        lapped = torch.isfinite(s[7])
-        one = lambda x: x.reshape(1).to(torch.float64)
-        return torch.cat([torch.full((1,), float(self.num_envs), dtype=torch.float64, device=self.device), one(s[0].sum()),
-                          one(s[0].min()), one(s[0].max()), one(s[1].sum()), one(s[2].sum()), one(s[3].sum()),
-                          one((s[4] == float(_capi.PC_FIRST_TERMINATED)).sum()), one(s[5].sum()), one(s[6].min()), one(lapped.sum()),
-                          one(torch.where(lapped, s[7], torch.zeros_like(s[7])).sum()), one(self._range)])
+        return state_totals(self.state, self._range)
 
     def shield_totals(self):
         """Evaluator(shield_depth=d): float64 [3] on the device, no host synchronisation -- the steps of the first episodes of the last
