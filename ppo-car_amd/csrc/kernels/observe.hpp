@@ -4,23 +4,10 @@
 // state is written.
 #pragma once
 
-// How many 5-degree turns either way of the start angle pc_env_observe_poses maps onto an F64 handle's rotation table (an
-// episode makes at most 1000 turns, car_env.py:749: the table holds no rotation further out).
-constexpr int PC_OBSERVE_TURNS = 1000;
-
-// The poses of one pc_env_observe_poses call (device arrays of M entries).  The STATE form of the kernel reads the handle's own
-// arrays instead and uses only M, n_tracks and lg.
-struct ObservePoses {
-    const double* __restrict__ px;
-    const double* __restrict__ py;
-    const double* __restrict__ vx;           // or nullptr: 0
-    const double* __restrict__ vy;           // or nullptr: 0
-    const int32_t* __restrict__ turns;       // heading = the track's start angle + 5 degrees * turns
-    const uint8_t* __restrict__ track_id;    // or nullptr: track 0
-    const int* __restrict__ turn_row;        // F64 handles: [n_tracks][2 * PC_OBSERVE_TURNS + 1] row of the rotation table, -1 = none
-    int64_t M;
-    int n_tracks;
-    int lg;                                  // log2(lanes per pose)
+// The poses of one pc_env_observe_poses call: PoseRows (car_step.hpp) without next_gate, time_step and active.  The STATE form of the
+// kernel reads the handle's own arrays instead and uses only M, n_tracks and lg.
+struct ObservePoses : PoseRows {
+    int lg;      // log2(lanes per pose)
 };
 
 // One pose on track `trk` (the same in every active lane), by the 2^lg lanes of its group: lane g measures rays g, g + G, ...
@@ -72,9 +59,8 @@ __device__ __forceinline__ void observe_pose(const EnvParams<T>& p, const int tr
 }
 
 // STATE = false: pose m of `q`.  STATE = true: env m of the handle, heading as env_step_core takes it (k, and rot on F64 handles).
-// A wave whose poses share a track runs the body once with that track's records in SGPRs; otherwise once per distinct track id
-// present (env_step_kernel<.., MIXED>'s waterfall).  The loop's mask is taken once, ahead of it, over lanes that all reach it: the
-// only lane-dependent exit before it is the bound on m, which whole groups take together.
+// One body pass per distinct track id present in a wave (for_each_track, car_step.hpp): the only exit before it is the bound on m,
+// which whole groups take together.
 template <typename T, bool STATE>
 __global__ __launch_bounds__(256) void observe_kernel(const EnvParams<T> p, const ObservePoses q, float* __restrict__ obs,
                                                       uint8_t* __restrict__ collides) {
@@ -82,21 +68,10 @@ __global__ __launch_bounds__(256) void observe_kernel(const EnvParams<T> p, cons
     const int64_t m = lane >> q.lg;
     const int g = (int)(lane & ((1 << q.lg) - 1));
     if (m >= q.M) return;
-    double px, py, vx, vy, rot = 0.0;
-    int k, trk;
-    if constexpr (STATE) {
-        const EnvRegs st = env_load<T>(p, m);
-        px = st.px; py = st.py; vx = st.vx; vy = st.vy; rot = st.rot;
-        k = st.k;
-        trk = p.track_id ? p.track_id[m] : 0;
-    } else {
-        px = q.px[m];
-        py = q.py[m];
-        vx = q.vx ? q.vx[m] : 0.0;
-        vy = q.vy ? q.vy[m] : 0.0;
-        k = q.turns[m];
-        trk = q.track_id ? q.track_id[m] : 0;
-    }
+    CarRegs st;
+    int next, trk;
+    bool act;      // (K17 has no `active` rows: every pose is observed)
+    load_pose<T>(p, q, STATE, m, st, next, trk, act);
     float* __restrict__ orow = obs + (size_t)m * p.D;
     uint8_t* __restrict__ crow = collides ? collides + m : nullptr;
     const bool known = trk < q.n_tracks;
@@ -104,22 +79,8 @@ __global__ __launch_bounds__(256) void observe_kernel(const EnvParams<T> p, cons
         for (int i = g; i < p.D; i += 1 << q.lg) orow[i] = 0.0f;
         if (g == 0 && crow) *crow = 0;
     }
-    uint64_t todo = __ballot(known);
-    while (todo) {
-        const int first = __ffsll((unsigned long long)todo) - 1;
-        const int cur = __builtin_amdgcn_readlane(trk, first);
-        const bool match = known & (trk == cur);
-        if (match) {
-            if constexpr (!STATE && sizeof(T) == 8) {
-                // F64 handles: the turn count's row of the rotation table (the host walked start_rot +- 5.0 that many times, as
-                // Car.move_car does); a count beyond the table takes start_rot + 5.0 * turns through the hash / the device's cos, sin
-                const int t = k;
-                rot = p.hdr[cur].start_rot + 5.0 * (double)t;
-                k = (t >= -PC_OBSERVE_TURNS && t <= PC_OBSERVE_TURNS && q.turn_row)
-                        ? q.turn_row[(size_t)cur * (2 * PC_OBSERVE_TURNS + 1) + (size_t)(t + PC_OBSERVE_TURNS)] : -1;
-            }
-            observe_pose<T>(p, cur, g, q.lg, px, py, vx, vy, k, rot, orow, crow);
-        }
-        todo &= ~__ballot(match);
-    }
+    for_each_track(known, trk, [&](const int cur) {
+        if constexpr (!STATE) resolve_turns<T>(p, cload(p.hdr + cur), cur, q.turn_row, st);
+        observe_pose<T>(p, cur, g, q.lg, st.px, st.py, st.vx, st.vy, st.k, st.rot, orow, crow);
+    });
 }

@@ -76,6 +76,7 @@
 // ---- the kernels, in dependency order (one translation unit: every kernel is compiled with this file's flags) ----
 #include "kernels/env_math.hpp"
 #include "kernels/env_step.hpp"
+#include "kernels/car_step.hpp"
 #include "kernels/observe.hpp"
 #include "kernels/step_poses.hpp"
 #include "kernels/safe_actions.hpp"
@@ -537,6 +538,24 @@ static int greedy_small(int KS, int rpl, bool epw16, bool rden, RolloutLaunch& o
     return PC_OK;
 }
 
+// The state rows of a K17 / K20 / K21 / K22 call: the caller's arrays (px == nullptr: the STATE form, M = the handle's env count; an
+// array the call does not have: nullptr, the kernels' default) and what the handle adds
+template <bool RW>
+static PoseRowsT<RW> pose_rows(const pc_env* e, RowPtr<RW, double> px, RowPtr<RW, double> py, RowPtr<RW, double> vx, RowPtr<RW, double> vy,
+                               RowPtr<RW, int32_t> turns, RowPtr<RW, int32_t> next_gate, RowPtr<RW, int32_t> time_step,
+                               const uint8_t* track_id, const uint8_t* active, int64_t M) {
+    return {px, py, vx, vy, turns, next_gate, time_step, track_id, active, e->turn_row, M, e->n_tracks};
+}
+static PoseRows state_rows(const pc_env* e) { return pose_rows<false>(e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, e->N); }
+
+// 256-thread blocks for M rows of per_row lanes each: refused where the count does not fit a grid's x dimension (which also keeps
+// M * per_row inside an int64_t)
+static int lanes_grid(const int64_t M, const int64_t per_row, unsigned& blocks) {
+    if (M > (int64_t)INT_MAX * 256 / per_row) return PC_ERR_UNSUPPORTED;
+    blocks = (unsigned)((M * per_row + 255) / 256);
+    return PC_OK;
+}
+
 // K17, K20: lanes per pose and the grid -- enough to fill the device at small M (the rule of choose_geometry), never more than rays, one at large M; the
 // handle's pc_env_set_lanes_per_env override applies (every choice writes the same bytes: a ray's value does not depend on its lane)
 static int pose_geometry(const pc_env* e, const int64_t M, int& lg, unsigned& blocks) {
@@ -548,11 +567,7 @@ static int pose_geometry(const pc_env* e, const int64_t M, int& lg, unsigned& bl
     }
     lg = 0;
     while ((1 << lg) < G) ++lg;
-    if (M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
-    const int64_t b = ((M << lg) + 255) / 256;
-    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
-    blocks = (unsigned)b;
-    return PC_OK;
+    return lanes_grid(M, 1 << lg, blocks);
 }
 
 template <typename T, bool STATE>
@@ -560,8 +575,6 @@ static int observe_launch(const pc_env* e, ObservePoses q, float* obs, uint8_t* 
     unsigned blocks;
     const int rc = pose_geometry(e, q.M, q.lg, blocks);
     if (rc != PC_OK) return rc;
-    q.n_tracks = e->n_tracks;
-    q.turn_row = e->turn_row;
     hipLaunchKernelGGL((observe_kernel<T, STATE>), dim3(blocks), dim3(256), 0, st, e->params<T>(), q, obs, collides);
     HIPCHK(hipGetLastError());
     return PC_OK;
@@ -573,8 +586,6 @@ static int step_poses_launch(const pc_env* e, StepPoses q, float* obs, hipStream
     unsigned blocks;
     const int rc = pose_geometry(e, q.M, q.lg, blocks);
     if (rc != PC_OK) return rc;
-    q.n_tracks = e->n_tracks;
-    q.turn_row = e->turn_row;
     hipLaunchKernelGGL((step_poses_kernel<T>), dim3(blocks), dim3(256), 0, st, e->params<T>(), q, obs);
     HIPCHK(hipGetLastError());
     return PC_OK;
@@ -582,13 +593,11 @@ static int step_poses_launch(const pc_env* e, StepPoses q, float* obs, hipStream
 
 // K21: one lane per (state, first action), 256 threads; a kernel per search depth (the recursion below the first action is compile-time)
 template <typename T>
-static int safe_actions_launch(const pc_env* e, SafeActions q, const int depth, uint8_t* safe, hipStream_t st) {
-    if (q.M > (INT64_MAX >> 7)) return PC_ERR_UNSUPPORTED;
-    const int64_t b = (q.M * 9 + 255) / 256;
-    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
-    q.n_tracks = e->n_tracks;
-    q.turn_row = e->turn_row;
-    const dim3 grid((unsigned)b), block(256);
+static int safe_actions_launch(const pc_env* e, const SafeActions& q, const int depth, uint8_t* safe, hipStream_t st) {
+    unsigned blocks;
+    const int rc = lanes_grid(q.M, 9, blocks);
+    if (rc != PC_OK) return rc;
+    const dim3 grid(blocks), block(256);
     switch (depth) {
         case 1: hipLaunchKernelGGL((safe_actions_kernel<T, 1>), grid, block, 0, st, e->params<T>(), q, safe); break;
         case 2: hipLaunchKernelGGL((safe_actions_kernel<T, 2>), grid, block, 0, st, e->params<T>(), q, safe); break;
@@ -601,19 +610,38 @@ static int safe_actions_launch(const pc_env* e, SafeActions q, const int depth, 
 
 // K22: one lane per (state, sequence), 256 threads; then, where a best_* array is asked for, a wave per state over what the first stored
 template <typename T>
-static int sequences_launch(const pc_env* e, Sequences q, hipStream_t st) {
-    if (q.M > (INT64_MAX >> 13)) return PC_ERR_UNSUPPORTED;
-    const int64_t b = (q.M * q.K + 255) / 256;
-    if (b > INT_MAX) return PC_ERR_UNSUPPORTED;
-    q.n_tracks = e->n_tracks;
-    q.turn_row = e->turn_row;
+static int sequences_launch(const pc_env* e, const Sequences& q, hipStream_t st) {
+    unsigned blocks;
+    const int rc = lanes_grid(q.M, q.K, blocks);
+    if (rc != PC_OK) return rc;
     const EnvParams<T> p = e->params<T>();
-    hipLaunchKernelGGL((sequences_kernel<T>), dim3((unsigned)b), dim3(256), 0, st, p, q);
+    hipLaunchKernelGGL((sequences_kernel<T>), dim3(blocks), dim3(256), 0, st, p, q);
     HIPCHK(hipGetLastError());
     if (q.best_k || q.best_action || q.best_ret) {
         hipLaunchKernelGGL(sequences_best_kernel, dim3((unsigned)((q.M + 3) / 4)), dim3(256), 0, st, q, p.track_id);
         HIPCHK(hipGetLastError());
     }
+    return PC_OK;
+}
+
+// f(T{}) with T the handle's arithmetic: f is a generic lambda that names the launch's instance by decltype of its argument
+template <typename F>
+static int by_dtype(const pc_env* e, F&& f) {
+    return e->dtype == PC_DTYPE_F64 ? f(double{}) : f(float{});
+}
+
+// K22's arguments past the states, shared by its two entry points: refused before the handle is looked at, else filled into q
+static int sequences_args(Sequences& q, const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale, double* ret,
+                          int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k, int64_t* best_action,
+                          double* best_ret) {
+    if (!actions || !ret || !steps || !status) return PC_ERR_INVALID_ARG;
+    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
+    if (H < 1 || H > PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
+    if (actions_state_stride != 0 && actions_state_stride != (int64_t)H * K) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    q.actions = actions; q.state_stride = actions_state_stride; q.K = K; q.H = H; q.reward_scale = reward_scale;
+    q.ret = ret; q.steps = steps; q.status = status; q.gates = gates; q.laps = laps;
+    q.best_k = best_k; q.best_action = best_action; q.best_ret = best_ret;
     return PC_OK;
 }
 
@@ -942,10 +970,8 @@ int pc_env_observe_poses(const pc_env* e, const double* px, const double* py, co
     if (!e || !px || !py || !turns || !obs || M < 1) return PC_ERR_INVALID_ARG;      // (before the handle is looked at)
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    ObservePoses q{};
-    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.track_id = track_id; q.M = M;
-    return e->dtype == PC_DTYPE_F64 ? observe_launch<double, false>(e, q, obs, collides, (hipStream_t)stream)
-                                    : observe_launch<float, false>(e, q, obs, collides, (hipStream_t)stream);
+    const ObservePoses q{pose_rows<false>(e, px, py, vx, vy, turns, nullptr, nullptr, track_id, nullptr, M), 0};
+    return by_dtype(e, [&](auto t) { return observe_launch<decltype(t), false>(e, q, obs, collides, (hipStream_t)stream); });
 }
 
 int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, double* vy, int32_t* turns, int32_t* next_gate,
@@ -960,12 +986,9 @@ int pc_env_step_poses(const pc_env* e, double* px, double* py, double* vx, doubl
     if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    StepPoses q{};
-    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.next_gate = next_gate; q.time_step = time_step;
-    q.track_id = track_id; q.actions = actions; q.active = active; q.M = M; q.reward_scale = reward_scale;
-    q.reward = reward; q.terminated = terminated; q.truncated = truncated; q.gate = gate;
-    return e->dtype == PC_DTYPE_F64 ? step_poses_launch<double>(e, q, obs, (hipStream_t)stream)
-                                    : step_poses_launch<float>(e, q, obs, (hipStream_t)stream);
+    const StepPoses q{pose_rows<true>(e, px, py, vx, vy, turns, next_gate, time_step, track_id, active, M),
+                      actions, reward, terminated, truncated, gate, reward_scale, 0};
+    return by_dtype(e, [&](auto t) { return step_poses_launch<decltype(t)>(e, q, obs, (hipStream_t)stream); });
 }
 
 int pc_env_safe_actions(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
@@ -978,10 +1001,8 @@ int pc_env_safe_actions(const pc_env* e, const double* px, const double* py, con
     if (depth < 1 || depth > PC_SAFE_MAX_DEPTH) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    SafeActions q{};
-    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.time_step = time_step; q.track_id = track_id; q.active = active; q.M = M;
-    return e->dtype == PC_DTYPE_F64 ? safe_actions_launch<double>(e, q, depth, safe, (hipStream_t)stream)
-                                    : safe_actions_launch<float>(e, q, depth, safe, (hipStream_t)stream);
+    const SafeActions q = pose_rows<false>(e, px, py, vx, vy, turns, nullptr, time_step, track_id, active, M);
+    return by_dtype(e, [&](auto t) { return safe_actions_launch<decltype(t)>(e, q, depth, safe, (hipStream_t)stream); });
 }
 
 int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream) {
@@ -990,10 +1011,8 @@ int pc_env_safe_actions_state(pc_env* e, int depth, uint8_t* safe, void* stream)
     if (depth < 1 || depth > PC_SAFE_MAX_DEPTH) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    SafeActions q{};      // (px == nullptr: the kernel reads the handle's own state)
-    q.M = e->N;
-    return e->dtype == PC_DTYPE_F64 ? safe_actions_launch<double>(e, q, depth, safe, (hipStream_t)stream)
-                                    : safe_actions_launch<float>(e, q, depth, safe, (hipStream_t)stream);
+    const SafeActions q = state_rows(e);
+    return by_dtype(e, [&](auto t) { return safe_actions_launch<decltype(t)>(e, q, depth, safe, (hipStream_t)stream); });
 }
 
 int pc_env_rollout_sequences(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
@@ -1003,21 +1022,14 @@ int pc_env_rollout_sequences(const pc_env* e, const double* px, const double* py
                              double* best_ret, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!e) return PC_ERR_INVALID_ARG;      // (this and the refusals below come before the handle is looked at)
-    if (!px || !py || !vx || !vy || !turns || !actions || !ret || !steps || !status) return PC_ERR_INVALID_ARG;
-    if (M < 1) return PC_ERR_INVALID_ARG;
-    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
-    if (H < 1 || H > PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
-    if (actions_state_stride != 0 && actions_state_stride != (int64_t)H * K) return PC_ERR_INVALID_ARG;
-    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    if (!px || !py || !vx || !vy || !turns || M < 1) return PC_ERR_INVALID_ARG;
+    Sequences q{};
+    const int rc = sequences_args(q, actions, actions_state_stride, K, H, reward_scale, ret, steps, status, gates, laps, best_k, best_action, best_ret);
+    if (rc != PC_OK) return rc;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    Sequences q{};
-    q.px = px; q.py = py; q.vx = vx; q.vy = vy; q.turns = turns; q.next_gate = next_gate; q.time_step = time_step;
-    q.track_id = track_id; q.active = active; q.M = M;
-    q.actions = actions; q.state_stride = actions_state_stride; q.K = K; q.H = H; q.reward_scale = reward_scale;
-    q.ret = ret; q.steps = steps; q.status = status; q.gates = gates; q.laps = laps;
-    q.best_k = best_k; q.best_action = best_action; q.best_ret = best_ret;
-    return e->dtype == PC_DTYPE_F64 ? sequences_launch<double>(e, q, (hipStream_t)stream) : sequences_launch<float>(e, q, (hipStream_t)stream);
+    static_cast<PoseRows&>(q) = pose_rows<false>(e, px, py, vx, vy, turns, next_gate, time_step, track_id, active, M);
+    return by_dtype(e, [&](auto t) { return sequences_launch<decltype(t)>(e, q, (hipStream_t)stream); });
 }
 
 int pc_env_rollout_sequences_state(pc_env* e, const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale,
@@ -1025,19 +1037,13 @@ int pc_env_rollout_sequences_state(pc_env* e, const uint8_t* actions, int64_t ac
                                    int64_t* best_action, double* best_ret, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!e) return PC_ERR_INVALID_ARG;
-    if (!actions || !ret || !steps || !status) return PC_ERR_INVALID_ARG;
-    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
-    if (H < 1 || H > PC_TIME_LIMIT) return PC_ERR_INVALID_ARG;
-    if (actions_state_stride != 0 && actions_state_stride != (int64_t)H * K) return PC_ERR_INVALID_ARG;
-    if (!std::isfinite(reward_scale)) return PC_ERR_INVALID_ARG;
+    Sequences q{};
+    const int rc = sequences_args(q, actions, actions_state_stride, K, H, reward_scale, ret, steps, status, gates, laps, best_k, best_action, best_ret);
+    if (rc != PC_OK) return rc;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    Sequences q{};      // (px == nullptr: the kernel reads the handle's own state)
-    q.M = e->N;
-    q.actions = actions; q.state_stride = actions_state_stride; q.K = K; q.H = H; q.reward_scale = reward_scale;
-    q.ret = ret; q.steps = steps; q.status = status; q.gates = gates; q.laps = laps;
-    q.best_k = best_k; q.best_action = best_action; q.best_ret = best_ret;
-    return e->dtype == PC_DTYPE_F64 ? sequences_launch<double>(e, q, (hipStream_t)stream) : sequences_launch<float>(e, q, (hipStream_t)stream);
+    static_cast<PoseRows&>(q) = state_rows(e);
+    return by_dtype(e, [&](auto t) { return sequences_launch<decltype(t)>(e, q, (hipStream_t)stream); });
 }
 
 int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {
@@ -1045,10 +1051,8 @@ int pc_env_observe(pc_env* e, float* obs, uint8_t* collides, void* stream) {
     if (!e || !obs) return PC_ERR_INVALID_ARG;
     DeviceGuard guard(e->device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
-    ObservePoses q{};
-    q.M = e->N;
-    return e->dtype == PC_DTYPE_F64 ? observe_launch<double, true>(e, q, obs, collides, (hipStream_t)stream)
-                                    : observe_launch<float, true>(e, q, obs, collides, (hipStream_t)stream);
+    const ObservePoses q{state_rows(e), 0};
+    return by_dtype(e, [&](auto t) { return observe_launch<decltype(t), true>(e, q, obs, collides, (hipStream_t)stream); });
 }
 
 int pc_env_info(pc_env* e, int32_t* gates_passed, int32_t* time_passed, void* stream) {

@@ -198,6 +198,19 @@ class VecCarEnv:
                              f"{tuple(t.shape)} {t.dtype} {t.device}")
         return t.data_ptr()
 
+    _ROW_DTYPES = {"track_id": torch.uint8, "active": torch.uint8, "actions": torch.int64}
+
+    def _pose_args(self, what, px, py, vx, vy, turns, noun="states", **rows):
+        """M and the pointers of a call's state rows: px, py, vx, vy float64 and turns int32, then `rows` in the order given (track_id,
+        active uint8; actions int64; anything else int32), each of M entries or None."""
+        if px.dim() != 1 or px.numel() < 1:
+            raise ValueError(f"{what}: px must be a 1-d tensor of M >= 1 {noun}, got {tuple(px.shape)}")
+        M = px.numel()
+        ptrs = [self._ptr(t, torch.float64, M, name) for name, t in (("px", px), ("py", py), ("vx", vx), ("vy", vy))]
+        ptrs.append(self._ptr(turns, torch.int32, M, "turns"))
+        ptrs += [self._ptr(t, self._ROW_DTYPES.get(name, torch.int32), M, name) for name, t in rows.items()]
+        return M, ptrs
+
     # ---- gymnasium-style surface ----------------------------------------------------------------
     def reset(self, seed=None, options=None, out=None):
         """seed is accepted and ignored, as in the reference (the env is deterministic, car_env.py:617)."""
@@ -313,15 +326,11 @@ class VecCarEnv:
         turns int32 (heading = the track's start angle + 5 degrees * turns), track_id uint8 (default track 0): device tensors of M
         entries, M independent of num_envs.  collides: an optional [M] uint8 tensor for Car.check_collision.  A pose whose track_id
         this env does not have gets a row of zeros.  The env state is neither read nor written; one launch, no synchronisation."""
-        if px.dim() != 1 or px.numel() < 1:
-            raise ValueError(f"observe_poses: px must be a 1-d tensor of M >= 1 poses, got {tuple(px.shape)}")
-        M, D = px.numel(), self.obs_dim
+        M, rows = self._pose_args("observe_poses", px, py, vx, vy, turns, noun="poses", track_id=track_id)
+        D = self.obs_dim
         obs = out if out is not None else self._new(M, D)
-        check(lib.pc_env_observe_poses(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
-                                       self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
-                                       self._ptr(turns, torch.int32, M, "turns"), self._ptr(track_id, torch.uint8, M, "track_id"), M,
-                                       self._ptr(obs, torch.float32, M * D, "obs"), self._ptr(collides, torch.uint8, M, "collides"),
-                                       self._stream()), "pc_env_observe_poses")
+        check(lib.pc_env_observe_poses(self._h, *rows, M, self._ptr(obs, torch.float32, M * D, "obs"),
+                                       self._ptr(collides, torch.uint8, M, "collides"), self._stream()), "pc_env_observe_poses")
         return obs
 
     # ---- stepping without committing (pc_env_step_poses) ----------------------------------------------------------------------
@@ -333,23 +342,18 @@ class VecCarEnv:
         float32, reward [M] float32, terminated, truncated, gate [M] uint8) or None to allocate.  Returns StepPoses(obs, reward,
         terminated, truncated, gate, next_gate, time_step).  A row whose track_id this env does not have gets zeros and keeps its
         state.  The env's own state is neither read nor written; one launch, no synchronisation."""
-        if px.dim() != 1 or px.numel() < 1:
-            raise ValueError(f"step_poses: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
-        M, D = px.numel(), self.obs_dim
         if next_gate is None:
-            next_gate = torch.zeros(M, dtype=torch.int32, device=self.device)
+            next_gate = torch.zeros_like(px, dtype=torch.int32, device=self.device)
         if time_step is None:
-            time_step = torch.zeros(M, dtype=torch.int32, device=self.device)
+            time_step = torch.zeros_like(px, dtype=torch.int32, device=self.device)
+        M, rows = self._pose_args("step_poses", px, py, vx, vy, turns, next_gate=next_gate, time_step=time_step, track_id=track_id,
+                                  actions=actions, active=active)
+        D = self.obs_dim
         if out is None:
             out = (self._new(M, D), self._new(M), self._new(M, dtype=torch.uint8), self._new(M, dtype=torch.uint8),
                    self._new(M, dtype=torch.uint8))
         obs, rew, term, trunc, gate = out
-        check(lib.pc_env_step_poses(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
-                                    self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
-                                    self._ptr(turns, torch.int32, M, "turns"), self._ptr(next_gate, torch.int32, M, "next_gate"),
-                                    self._ptr(time_step, torch.int32, M, "time_step"), self._ptr(track_id, torch.uint8, M, "track_id"),
-                                    self._ptr(actions, torch.int64, M, "actions"), self._ptr(active, torch.uint8, M, "active"), M,
-                                    self.reward_scaling, self._ptr(obs, torch.float32, M * D, "obs"),
+        check(lib.pc_env_step_poses(self._h, *rows, M, self.reward_scaling, self._ptr(obs, torch.float32, M * D, "obs"),
                                     self._ptr(rew, torch.float32, M, "reward"), self._ptr(term, torch.uint8, M, "terminated"),
                                     self._ptr(trunc, torch.uint8, M, "truncated"), self._ptr(gate, torch.uint8, M, "gate"),
                                     self._stream()), "pc_env_step_poses")
@@ -363,15 +367,10 @@ class VecCarEnv:
         time_step int32 (default 0), track_id uint8 (default track 0), active uint8 (default every row; a row with 0 keeps its 9 bytes):
         device tensors of M entries, all read only.  out: a [M, 9] uint8 tensor to fill (the returned bool tensor is a view of it).  A row
         whose track_id this env does not have is all false.  The env state is neither read nor written; one launch, no synchronisation."""
-        if px.dim() != 1 or px.numel() < 1:
-            raise ValueError(f"safe_actions: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
-        M = px.numel()
+        M, rows = self._pose_args("safe_actions", px, py, vx, vy, turns, time_step=time_step, track_id=track_id, active=active)
         safe = out if out is not None else self._new(M, 9, dtype=torch.uint8)
-        check(lib.pc_env_safe_actions(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
-                                      self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
-                                      self._ptr(turns, torch.int32, M, "turns"), self._ptr(time_step, torch.int32, M, "time_step"),
-                                      self._ptr(track_id, torch.uint8, M, "track_id"), self._ptr(active, torch.uint8, M, "active"), M,
-                                      int(depth), self._ptr(safe, torch.uint8, M * 9, "out"), self._stream()), "pc_env_safe_actions")
+        check(lib.pc_env_safe_actions(self._h, *rows, M, int(depth), self._ptr(safe, torch.uint8, M * 9, "out"), self._stream()),
+              "pc_env_safe_actions")
         return safe.view(torch.bool)
 
     def action_masks(self, depth=1, out=None):
@@ -417,15 +416,10 @@ class VecCarEnv:
         of the row's maximum), best_action int64 (its first action), best_ret float64, each [M].  out: a dict of tensors to fill; with
         `out` given, an optional key it lacks (gates, laps, best_*) is not computed.  A row whose track_id this env does not have gets
         zeros (best_action 8).  The env state is neither read nor written; no synchronisation."""
-        if px.dim() != 1 or px.numel() < 1:
-            raise ValueError(f"rollout_sequences: px must be a 1-d tensor of M >= 1 states, got {tuple(px.shape)}")
-        M = px.numel()
+        M, rows = self._pose_args("rollout_sequences", px, py, vx, vy, turns, next_gate=next_gate, time_step=time_step, track_id=track_id,
+                                  active=active)
         args, res = self._sequence_args("rollout_sequences", M, actions, reward_scale, out)
-        check(lib.pc_env_rollout_sequences(self._h, self._ptr(px, torch.float64, M, "px"), self._ptr(py, torch.float64, M, "py"),
-                                           self._ptr(vx, torch.float64, M, "vx"), self._ptr(vy, torch.float64, M, "vy"),
-                                           self._ptr(turns, torch.int32, M, "turns"), self._ptr(next_gate, torch.int32, M, "next_gate"),
-                                           self._ptr(time_step, torch.int32, M, "time_step"), self._ptr(track_id, torch.uint8, M, "track_id"),
-                                           self._ptr(active, torch.uint8, M, "active"), M, *args), "pc_env_rollout_sequences")
+        check(lib.pc_env_rollout_sequences(self._h, *rows, M, *args), "pc_env_rollout_sequences")
         return res
 
     def score_sequences(self, actions, reward_scale=None, out=None):
