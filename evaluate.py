@@ -26,6 +26,10 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
                                                                      # no checkpoint: the first episodes of 1024 envs under a random-shooting
                                                                      # planner on the env's own model (ppo_car_amd.PlannerEvaluator), the same
                                                                      # eval/* scalars: the model-based baseline a policy's figures stand beside
+    python evaluate.py --planner cem --plan-iterations 4 --plan-elites 8 [--plan-horizon 16] [--plan-candidates 64] --envs 1024
+                                                                     # ... under the cross-entropy planner (ppo_car_amd.CEMPlanner): 4 rounds
+                                                                     # of 64 sequences per step, each env's action weights refitted to its 8
+                                                                     # best; both options must be given: they are the split of the budget
 """
 import argparse
 import json
@@ -68,17 +72,23 @@ def parse_args(argv=None):
     ap.add_argument("--video-scale", type=int, default=4, help="a video frame is 1280 / scale x 720 / scale per env: 1, 2, 4, 5, 8 or 10")
     ap.add_argument("--video-fps", type=int, default=30)
     # the planner's options appear in the namespace only when given: without --planner it is the namespace it always was
-    ap.add_argument("--planner", choices=("shooting",), default=argparse.SUPPRESS, help="--envs: evaluate a random-shooting planner on the env's own "
-                    "model (ppo_car_amd.PlannerEvaluator) instead of a checkpoint's policy")
+    ap.add_argument("--planner", choices=("shooting", "cem"), default=argparse.SUPPRESS, help="--envs: evaluate a planner on the env's own model "
+                    "(ppo_car_amd.PlannerEvaluator) instead of a checkpoint's policy: uniform random shooting, or the cross-entropy method "
+                    "(which takes --plan-iterations and --plan-elites)")
     ap.add_argument("--plan-horizon", type=int, default=argparse.SUPPRESS, metavar="H", help="--planner: steps per candidate sequence (default 16)")
     ap.add_argument("--plan-candidates", type=int, default=argparse.SUPPRESS, metavar="K", help="--planner: sequences scored per env and step, "
-                    "the first 9 hold one action each (default 256)")
+                    "the first 9 hold one action each (default 256; --planner cem: per iteration, default 64)")
+    ap.add_argument("--plan-iterations", type=int, default=argparse.SUPPRESS, metavar="I", help="--planner cem: sample / score / refit rounds per step")
+    ap.add_argument("--plan-elites", type=int, default=argparse.SUPPRESS, metavar="E", help="--planner cem: the best sequences the weights are refitted to")
     args = ap.parse_args(argv)
     if not hasattr(args, "planner"):
         if args.checkpoint is None:
             ap.error("the following arguments are required: --checkpoint")
-        if hasattr(args, "plan_horizon") or hasattr(args, "plan_candidates"):
-            ap.error("--plan-horizon / --plan-candidates belong to --planner")
+        if any(hasattr(args, k) for k in ("plan_horizon", "plan_candidates", "plan_iterations", "plan_elites")):
+            ap.error("--plan-horizon / --plan-candidates / --plan-iterations / --plan-elites belong to --planner")
+    elif (args.planner == "cem") != hasattr(args, "plan_iterations") or (args.planner == "cem") != hasattr(args, "plan_elites"):
+        # the split of a step's budget into rounds and elites has no default on the command line: cem names both, shooting neither
+        ap.error("--planner cem takes --plan-iterations and --plan-elites, both of them, and --planner shooting neither")
     elif args.envs is None:
         raise ValueError("--planner evaluates the batched first episodes: pass --envs N")
     check_video_args(args)
@@ -183,13 +193,18 @@ def batched(pc, args):
 
 
 def planned(pc, args):
-    """--planner shooting --envs N: N first episodes under the shooting planner, the eval/* scalars of batched()."""
+    """--planner shooting | cem --envs N: N first episodes under the planner, the eval/* scalars of batched()."""
+    cem = args.planner == "cem"
+    more = dict(kind="cem", iterations=args.plan_iterations, elites=args.plan_elites) if cem else {}
     ev = pc.PlannerEvaluator(args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda",
-                             horizon=getattr(args, "plan_horizon", 16), candidates=getattr(args, "plan_candidates", 256), seed=args.seed)
+                             horizon=getattr(args, "plan_horizon", 16), candidates=getattr(args, "plan_candidates", 64 if cem else 256),
+                             seed=args.seed, **more)
     try:
         out = ev.evaluate()
         out["path"] = ev.last_path
         out["planner"] = {"kind": args.planner, "horizon": ev.planner.horizon, "candidates": ev.planner.candidates}
+        if cem:
+            out["planner"].update(iterations=ev.planner.iterations, elites=ev.planner.elites)
     finally:
         ev.close()
     print(json.dumps(out))

@@ -372,6 +372,39 @@ int pc_gae_bootstrap(int device, const float* rew, const float* val, const float
 int pc_sample(int device, const float* logits, int64_t N, int A, uint64_t seed, uint64_t offset, int64_t* actions,
               float* logprob, float* entropy, void* stream);
 
+/* ---- the cross-entropy method around pc_env_rollout_sequences (opt-in: the entry points above are untouched): draw every state's K
+ * action sequences from that state's own per-step distribution (K23), score them with pc_env_rollout_sequences on one table per state
+ * (actions_state_stride = H * K), move the distributions towards the E best sequences (K24), repeat.  All arithmetic is integer: the
+ * results are exact and do not depend on the launch geometry.  No env handle: a device index and a stream, as pc_sample.  All DEVICE.
+ * WEIGHTS  uint32 [M][H][9]: the unnormalised probability of action a in step t of state m, 65536 = one.  Both calls read a value above
+ *   65536 as 65536 and a row [9] that sums to 0 as nine ones.
+ * pc_cem_sample: table uint8 [M][H][K], state m's at table + m * H * K in pc_env_rollout_sequences' time-major [H][K] layout.
+ *   Element (m, t, k) has idx = (m * H + t) * K + k.  With x = word (offset & 3) of THE STREAM's block for (seed, offset >> 2, idx) -- the
+ *   raw 32-bit word, not the float uniform --, S the row's weight sum and r = ((uint64_t)x * S) >> 32, the action is the least a with
+ *   r < w[0] + ... + w[a].  An action of weight 0 is never drawn.
+ *   const_columns != 0   columns k < min(K, 9) hold the constant action k instead
+ *   keep                 uint8 [M][H] or NULL; given and K > 9: column 9 holds keep[m][t], copied as stored
+ *   active               uint8 [M] or NULL = every row; NOTHING of a row with 0 is written
+ * pc_cem_refit: per state, from ret [M][K] float64 (pc_env_rollout_sequences' output) and the table those returns belong to:
+ *   1. the K sequences in the order "ret descending, then k ascending", values compared as float64 (-0.0 == 0.0; ret holds no NaN)
+ *   2. the elites are the first E of that order
+ *   3. c[t][a] = the number of elites whose table entry at step t is a (an entry above 8 counts as 8, as it acts)
+ *   4. f = (c << 16) / E, integer division
+ *   5. w' = min(65536, max(w_min, w - (w >> shift) + (f >> shift))), written in place (w as read: see WEIGHTS).  shift = 0 replaces the
+ *      weights by the elites' frequencies, a larger shift moves them a 2^-shift part of the way
+ *   6. best_seq uint8 [M][H] or NULL: the rank-0 column of the table, copied as stored
+ *   active as above: a row with 0 is not touched.  ret, table and active are only read.
+ *   One workgroup per state; the E-th key by 8-bit radix passes in LDS, ties at the threshold by a prefix count in k order.
+ * Limits: M >= 1; H 1 .. PC_CEM_MAX_HORIZON; K 1 .. PC_SEQ_MAX_CANDIDATES; E 1 .. K; shift 0 .. 16; w_min 0 .. 65536.
+ * Checked before any device call, in this order: NULL weights / table (pc_cem_refit: weights / ret / table); M < 1; H outside its
+ * limits; K outside its limits; then for pc_cem_refit E, shift, w_min: PC_ERR_INVALID_ARG; then the device (PC_ERR_NO_DEVICE); a grid
+ * the device cannot take (M * H * K above 2^39; pc_cem_refit: M above 2^31 - 1): PC_ERR_UNSUPPORTED.  Neither call synchronises. */
+#define PC_CEM_MAX_HORIZON 256
+int pc_cem_sample(int device, const uint32_t* weights, int64_t M, int H, int K, uint64_t seed, uint64_t offset, int const_columns,
+                  const uint8_t* keep, const uint8_t* active, uint8_t* table, void* stream);
+int pc_cem_refit(int device, uint32_t* weights, const double* ret, const uint8_t* table, int64_t M, int H, int K, int E, int shift,
+                 int w_min, const uint8_t* active, uint8_t* best_seq, void* stream);
+
 /* ---- batched evaluation (opt-in: the entry points above are untouched): the FIRST episode of every env and its lap times, and the
  * deterministic action.  What the reference's log_video answers with one fresh episode (train.py:23-50) and every PPO library with
  * evaluate_policy: N fresh episodes from the start line, one per env.

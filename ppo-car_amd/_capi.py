@@ -29,6 +29,8 @@ PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppoc
 PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_SAFE_MAX_DEPTH = 4    # pc_env_safe_actions: the deepest search (include/ppocar.h)
 PC_SEQ_MAX_CANDIDATES = 4096     # pc_env_rollout_sequences: the most sequences per state (include/ppocar.h)
+PC_CEM_MAX_HORIZON = 256         # pc_cem_sample / pc_cem_refit: the longest horizon (include/ppocar.h)
+PC_CEM_W_MAX = 65536             # ... the largest weight: a probability of one
 PC_TIME_LIMIT = 1000    # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
 PC_OPT_ROLLOUT_FORM, PC_OPT_ROLLOUT_EPW, PC_OPT_ROLLOUT_FAST = 1, 2, 3
 PC_KERNEL_NAMES = {0: "none", 1: "K9", 2: "K9s", 3: "K9-literal", 4: "K9d-filter", 5: "K9s-literal", 6: "K9d-selector", 7: "K9m", 8: "K9m-literal"}     # pc_env_last_rollout_kernel
@@ -103,6 +105,8 @@ _sig = {
     "pc_gae_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_gae_bootstrap": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _i64, _i64, _vp, _vp, _d, _vp, _vp, _vp]),
     "pc_sample": (_i, [_i, _vp, _i64, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pc_cem_sample": (_i, [_i, _vp, _i64, _i, _i, C.c_uint64, C.c_uint64, _i, _vp, _vp, _vp, _vp]),
+    "pc_cem_refit": (_i, [_i, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pc_first_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp]),
     "pc_greedy": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "pc_track_maps": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),

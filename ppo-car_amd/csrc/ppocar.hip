@@ -82,6 +82,7 @@
 #include "kernels/safe_actions.hpp"
 #include "kernels/sequences.hpp"
 #include "kernels/gae_sample.hpp"
+#include "kernels/cem.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
 #include "kernels/render.hpp"
@@ -1283,6 +1284,47 @@ int pc_greedy(int device, const float* logits, int64_t N, int A, int64_t* action
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     hipLaunchKernelGGL(greedy_kernel<16>, dim3((int)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, N, A, actions,
                        action_f32, logprob);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+// K23 / K24: what both calls check of the table's shape, in the documented order
+static bool cem_shape_ok(int64_t M, int H, int K) {
+    return M >= 1 && H >= 1 && H <= PC_CEM_MAX_HORIZON && K >= 1 && K <= PC_SEQ_MAX_CANDIDATES;
+}
+
+int pc_cem_sample(int device, const uint32_t* weights, int64_t M, int H, int K, uint64_t seed, uint64_t offset, int const_columns,
+                  const uint8_t* keep, const uint8_t* active, uint8_t* table, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!weights || !table) return PC_ERR_INVALID_ARG;
+    if (!cem_shape_ok(M, H, K)) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    unsigned blocks;
+    const int rc = lanes_grid(M, (int64_t)H * K, blocks);
+    if (rc != PC_OK) return rc;
+    const CemSample q{weights, keep, active, table, M, H, K, const_columns, seed, offset};
+    hipLaunchKernelGGL(cem_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, q);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
+int pc_cem_refit(int device, uint32_t* weights, const double* ret, const uint8_t* table, int64_t M, int H, int K, int E, int shift,
+                 int w_min, const uint8_t* active, uint8_t* best_seq, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!weights || !ret || !table) return PC_ERR_INVALID_ARG;
+    if (!cem_shape_ok(M, H, K)) return PC_ERR_INVALID_ARG;
+    if (E < 1 || E > K) return PC_ERR_INVALID_ARG;
+    if (shift < 0 || shift > 16) return PC_ERR_INVALID_ARG;
+    if (w_min < 0 || w_min > (int)CEM_W_MAX) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    if (M > INT_MAX) return PC_ERR_UNSUPPORTED;      // one workgroup per state
+    const CemRefit q{weights, ret, table, active, best_seq, H, K, E, shift, (uint32_t)w_min};
+    const CemLds lds{K, H};
+    hipLaunchKernelGGL(cem_refit_kernel, dim3((unsigned)M), dim3(K <= 256 ? 64 : 256), lds.bytes(), (hipStream_t)stream, q);
     HIPCHK(hipGetLastError());
     return PC_OK;
 }

@@ -17,4 +17,4 @@ from .evaluation import Evaluator  # noqa: E402,F401
 from .track_maps import TrackMaps  # noqa: E402,F401
 from .landscape import PolicyLandscape  # noqa: E402,F401
 from .renderer import Renderer  # noqa: E402,F401
-from .planner import Planner, PlannerEvaluator  # noqa: E402,F401
+from .planner import CEMPlanner, Planner, PlannerEvaluator  # noqa: E402,F401
