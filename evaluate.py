@@ -30,6 +30,10 @@ log_video (train.py:23-50) without the renderer: one env, actions from the agent
                                                                      # ... under the cross-entropy planner (ppo_car_amd.CEMPlanner): 4 rounds
                                                                      # of 64 sequences per step, each env's action weights refitted to its 8
                                                                      # best; both options must be given: they are the split of the budget
+    python evaluate.py --planner cem ... --plan-horizon 4 --checkpoint model.dat --plan-gamma 0.99 --plan-bootstrap running
+                                                                     # ... scoring each sequence by its discounted return plus gamma^n * the
+                                                                     # checkpoint's critic at the state it ends in (running_truncated: also
+                                                                     # where it ends at the time limit); a bootstrap needs --checkpoint
 """
 import argparse
 import json
@@ -80,17 +84,25 @@ def parse_args(argv=None):
                     "the first 9 hold one action each (default 256; --planner cem: per iteration, default 64)")
     ap.add_argument("--plan-iterations", type=int, default=argparse.SUPPRESS, metavar="I", help="--planner cem: sample / score / refit rounds per step")
     ap.add_argument("--plan-elites", type=int, default=argparse.SUPPRESS, metavar="E", help="--planner cem: the best sequences the weights are refitted to")
+    ap.add_argument("--plan-gamma", type=float, default=argparse.SUPPRESS, metavar="G", help="--planner: discount of a sequence's rewards, 0 .. 1 (default 1)")
+    ap.add_argument("--plan-bootstrap", choices=("none", "running", "running_truncated"), default=argparse.SUPPRESS, help="--planner: add "
+                    "gamma^n * the critic's value of the state a sequence ends in, where it still runs (running) or also where it ended at the "
+                    "time limit (running_truncated); needs --checkpoint (default none)")
     args = ap.parse_args(argv)
     if not hasattr(args, "planner"):
         if args.checkpoint is None:
             ap.error("the following arguments are required: --checkpoint")
         if any(hasattr(args, k) for k in ("plan_horizon", "plan_candidates", "plan_iterations", "plan_elites")):
             ap.error("--plan-horizon / --plan-candidates / --plan-iterations / --plan-elites belong to --planner")
+        if hasattr(args, "plan_gamma") or hasattr(args, "plan_bootstrap"):
+            ap.error("--plan-gamma / --plan-bootstrap belong to --planner")
     elif (args.planner == "cem") != hasattr(args, "plan_iterations") or (args.planner == "cem") != hasattr(args, "plan_elites"):
         # the split of a step's budget into rounds and elites has no default on the command line: cem names both, shooting neither
         ap.error("--planner cem takes --plan-iterations and --plan-elites, both of them, and --planner shooting neither")
     elif args.envs is None:
         raise ValueError("--planner evaluates the batched first episodes: pass --envs N")
+    elif getattr(args, "plan_bootstrap", "none") != "none" and args.checkpoint is None:
+        ap.error("--plan-bootstrap other than none needs --checkpoint: the critic that values the end states")
     check_video_args(args)
     if args.shield and args.rollout_kernel == "mega":
         raise ValueError("--shield masks the action between the policy step and the env step: --rollout-kernel must be 'auto' or 'steps', not 'mega'")
@@ -196,6 +208,14 @@ def planned(pc, args):
     """--planner shooting | cem --envs N: N first episodes under the planner, the eval/* scalars of batched()."""
     cem = args.planner == "cem"
     more = dict(kind="cem", iterations=args.plan_iterations, elites=args.plan_elites) if cem else {}
+    critic = hasattr(args, "plan_gamma") or hasattr(args, "plan_bootstrap")
+    if critic:      # (without the two options: the call it always was)
+        more.update(gamma=getattr(args, "plan_gamma", 1.0), bootstrap=getattr(args, "plan_bootstrap", "none"))
+        if more["bootstrap"] != "none":
+            from ppo_car_amd.env import ray_count
+            agent = pc.Agent(6 + ray_count(args.num_rays), 9).cuda()
+            agent.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
+            more["agent"] = agent
     ev = pc.PlannerEvaluator(args.track, n_envs=args.envs, num_rays=args.num_rays, reward_scaling=1.0, device="cuda",
                              horizon=getattr(args, "plan_horizon", 16), candidates=getattr(args, "plan_candidates", 64 if cem else 256),
                              seed=args.seed, **more)
@@ -205,6 +225,8 @@ def planned(pc, args):
         out["planner"] = {"kind": args.planner, "horizon": ev.planner.horizon, "candidates": ev.planner.candidates}
         if cem:
             out["planner"].update(iterations=ev.planner.iterations, elites=ev.planner.elites)
+        if critic:
+            out["planner"].update(gamma=more["gamma"], bootstrap=more["bootstrap"])
     finally:
         ev.close()
     print(json.dumps(out))

@@ -270,6 +270,69 @@ int pc_env_rollout_sequences_state(pc_env* e, const uint8_t* actions, int64_t ac
                                    double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k,
                                    int64_t* best_action, double* best_ret, void* stream);
 
+/* ---- scoring action sequences with a discount and the critic's value of the state they end in (opt-in: the entry points above are
+ * untouched): the n-step return plus gamma^n * V(end state), the quantity the PPO loop's GAE estimates.  Three launches on the stream:
+ * K25 (K22's lane and loop with the discount, then the observation of the lane's end state), the policy step over end_obs, K26 (the
+ * combination and each state's best sequence).  Every argument pc_env_rollout_sequences[_state] takes keeps its meaning and its rules;
+ * in addition:
+ *   gamma        double, finite, 0 <= gamma <= 1
+ *   bootstrap    PC_SEQ_BOOTSTRAP_NONE: no lane; PC_SEQ_BOOTSTRAP_RUNNING: the lanes whose status is PC_FIRST_RUNNING after their last
+ *                step; PC_SEQ_BOOTSTRAP_RUNNING_TRUNCATED: those and the lanes that ended at the time limit (PC_FIRST_TRUNCATED), the
+ *                planning-side twin of the PPO loop's truncation_bootstrap = "final_obs".  A terminated lane is never bootstrapped,
+ *                a crash in the step in which the time limit falls due included.
+ *   p, image     the policy handle and the weight image it packed (pc_policy_pack), or NULL and NULL: allowed only with
+ *                PC_SEQ_BOOTSTRAP_NONE.  With a policy given, its D must be the env handle's obs dim and its device the env handle's.
+ *   workspace    DEVICE memory of pc_env_rollout_sequences_value_workspace(M, K) bytes, 16-byte aligned, for what the policy step
+ *                writes besides the value (its actions and log-probabilities); required with a policy, else ignored (may be NULL).
+ *                Nothing is allocated inside the call.  pc_env_rollout_sequences_value_workspace returns 0 for M < 1 or K outside
+ *                1 .. PC_SEQ_MAX_CANDIDATES.
+ * New outputs, per (state, sequence), [M][K], after the existing ones:
+ *   end_obs        float32 [M][K][D]: required with a policy, else optional
+ *   end_value      float32: required with a policy; without one it is not written
+ *   end_discount   float64 or NULL
+ *   ret_env        float64 or NULL
+ * Definitions.  Every arithmetic step is a separately rounded IEEE float64 operation, never contracted into an fma, so that plain numpy
+ * reproduces the bits:
+ *   ret = 0.0; disc = 1.0
+ *   every step a lane takes:   ret  = ret + disc * (double)r      r = the float32 scaled reward, as pc_env_rollout_sequences has it
+ *                              disc = disc * gamma
+ *   after its last step:       ret_env = ret;  end_discount = disc
+ *   end_obs[m][k]   = the observation CarEnv.step returned in the lane's LAST step taken: the observation of the pose the lane ends at
+ *                     (F32 handle: pc_env_step_poses' bits; F64 handle: the reference's), for every rolled-out lane, terminated ones
+ *                     included (the pose of the impact)
+ *   end_value       = what ONE pc_policy_act_greedy call over end_obs viewed as N = M * K rows writes to `value` (the form, and
+ *                     therefore the last bits, depend on N: it is one call, not one per state)
+ *   ret[m][k]       = ret_env + end_discount * (double)end_value      where the mode bootstraps the lane's status; else ret_env
+ *   best_k / best_action / best_ret: pc_env_rollout_sequences' rule (the lowest k of the maximum, compared as float64) on this ret
+ * Consequences:
+ *   - with gamma == 1.0, PC_SEQ_BOOTSTRAP_NONE and no policy every output equals pc_env_rollout_sequences' bit for bit;
+ *   - steps, status, gates and laps never depend on gamma, bootstrap or the policy;
+ *   - active[m] == 0: the row is not written in any array except end_value, which holds the policy step's output for whatever the
+ *     caller's end_obs memory held there and is unspecified;
+ *   - a track_id the handle does not have: pc_env_rollout_sequences' zeros, an end_obs row of zeros, end_discount 1, ret_env 0; the
+ *     lane is never bootstrapped (end_value is the policy's value of the zero observation).
+ * The second launch (K26) runs whenever a policy is given or a best_* array is asked for.
+ * Checked before any device call, in this order: everything pc_env_rollout_sequences[_state] checks, in its order; gamma not finite or
+ * outside 0 .. 1; a bootstrap other than the three; one of p / image NULL and the other not; a bootstrap without a policy; a policy
+ * without end_obs, end_value or workspace; a policy whose D or device is not the env handle's:
+ * PC_ERR_INVALID_ARG; then as pc_env_rollout_sequences and pc_policy_act_greedy.  Neither call synchronises. */
+#define PC_SEQ_BOOTSTRAP_NONE 0
+#define PC_SEQ_BOOTSTRAP_RUNNING 1
+#define PC_SEQ_BOOTSTRAP_RUNNING_TRUNCATED 2
+int64_t pc_env_rollout_sequences_value_workspace(int64_t M, int K);
+int pc_env_rollout_sequences_value(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy,
+                                   const int32_t* turns, const int32_t* next_gate, const int32_t* time_step, const uint8_t* track_id,
+                                   const uint8_t* active, int64_t M, const uint8_t* actions, int64_t actions_state_stride, int K, int H,
+                                   double reward_scale, double gamma, int bootstrap, const pc_policy* p, const float* image,
+                                   void* workspace, double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps,
+                                   int32_t* best_k, int64_t* best_action, double* best_ret, float* end_obs, float* end_value,
+                                   double* end_discount, double* ret_env, void* stream);
+int pc_env_rollout_sequences_value_state(pc_env* e, const uint8_t* actions, int64_t actions_state_stride, int K, int H,
+                                         double reward_scale, double gamma, int bootstrap, const pc_policy* p, const float* image,
+                                         void* workspace, double* ret, int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps,
+                                         int32_t* best_k, int64_t* best_action, double* best_ret, float* end_obs, float* end_value,
+                                         double* end_discount, double* ret_env, void* stream);
+
 /* Per-handle launch options of pc_rollout (below).  Every choice gives bit-identical buffers; they exist so that the variant a
  * benchmark size takes can be checked at other batch sizes, and for A/B timing.
  *   PC_OPT_ROLLOUT_FORM  -1 (default) automatic: above 8192 envs independent waves of 32 envs, 256 envs per workgroup (128 up to

@@ -29,6 +29,8 @@ PC_DIAG_FLOATS = 8       # pc_*_diag: the update-diagnostics block (include/ppoc
 PC_PPO_LARGE_MAX_B = 1 << 20     # pc_ppo_minibatch_large: the largest minibatch (include/ppocar.h)
 PC_SAFE_MAX_DEPTH = 4    # pc_env_safe_actions: the deepest search (include/ppocar.h)
 PC_SEQ_MAX_CANDIDATES = 4096     # pc_env_rollout_sequences: the most sequences per state (include/ppocar.h)
+PC_SEQ_BOOTSTRAP_NONE, PC_SEQ_BOOTSTRAP_RUNNING, PC_SEQ_BOOTSTRAP_RUNNING_TRUNCATED = 0, 1, 2     # pc_env_rollout_sequences_value (include/ppocar.h)
+SEQ_BOOTSTRAP = {"none": PC_SEQ_BOOTSTRAP_NONE, "running": PC_SEQ_BOOTSTRAP_RUNNING, "running_truncated": PC_SEQ_BOOTSTRAP_RUNNING_TRUNCATED}
 PC_CEM_MAX_HORIZON = 256         # pc_cem_sample / pc_cem_refit: the longest horizon (include/ppocar.h)
 PC_CEM_W_MAX = 65536             # ... the largest weight: a probability of one
 PC_TIME_LIMIT = 1000    # CarEnv's time limit (car_env.py:749): the slot of a truncation at rollout step t is t // PC_TIME_LIMIT
@@ -97,6 +99,9 @@ _sig = {
     "pc_env_safe_actions_state": (_i, [_vp, _i, _vp, _vp]),
     "pc_env_rollout_sequences": (_i, [_vp] * 10 + [_i64, _vp, _i64, _i, _i, _d] + [_vp] * 9),
     "pc_env_rollout_sequences_state": (_i, [_vp, _vp, _i64, _i, _i, _d] + [_vp] * 9),
+    "pc_env_rollout_sequences_value_workspace": (_i64, [_i64, _i]),
+    "pc_env_rollout_sequences_value": (_i, [_vp] * 10 + [_i64, _vp, _i64, _i, _i, _d, _d, _i, _vp, _vp, _vp] + [_vp] * 13),
+    "pc_env_rollout_sequences_value_state": (_i, [_vp, _vp, _i64, _i, _i, _d, _d, _i, _vp, _vp, _vp] + [_vp] * 13),
     "pc_build_ablate": (_i, []),
     "pc_env_get_state": (_i, [_vp] * 9),
     "pc_env_set_state": (_i, [_vp] * 9),

@@ -81,6 +81,7 @@
 #include "kernels/step_poses.hpp"
 #include "kernels/safe_actions.hpp"
 #include "kernels/sequences.hpp"
+#include "kernels/sequences_value.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/cem.hpp"
 #include "kernels/evaluation.hpp"
@@ -1614,6 +1615,95 @@ int pc_policy_act_greedy(const pc_policy* p, const float* obs, int64_t N, const 
     if (!p) return PC_ERR_INVALID_ARG;
     return policy_act_impl(p->device, p->precision, p->split, obs, N, p->D, p->H, p->A, image, 0, 0, nullptr, action, action_f32, logprob, value,
                            logits_out, stream, true);
+}
+
+}  // extern "C"
+
+// K25, the policy step, K26: one lane per (state, sequence) as K22; pc_policy_act_greedy's launch over end_obs as M * K rows, its actions
+// and log-probabilities into the caller's workspace; then a wave per state
+static int64_t sequences_value_ws_bytes(const int64_t M, const int K) { return ((M * K * 12 + 15) / 16) * 16; }
+
+template <typename T>
+static int sequences_value_launch(const pc_env* e, const SequencesValue& q, const pc_policy* pp, const float* image, void* workspace,
+                                  float* end_value, hipStream_t st) {
+    unsigned blocks;
+    const int rc = lanes_grid(q.M, q.K, blocks);
+    if (rc != PC_OK) return rc;
+    const EnvParams<T> p = e->params<T>();
+    hipLaunchKernelGGL((sequences_value_kernel<T>), dim3(blocks), dim3(256), 0, st, p, q);
+    HIPCHK(hipGetLastError());
+    if (pp) {
+        const int64_t N = q.M * q.K;
+        int64_t* action = static_cast<int64_t*>(workspace);
+        float* logprob = reinterpret_cast<float*>(action + N);
+        const int prc = policy_act_impl(pp->device, pp->precision, pp->split, q.end_obs, N, pp->D, pp->H, pp->A, image, 0, 0, nullptr, action,
+                                        nullptr, logprob, end_value, nullptr, st, true);
+        if (prc != PC_OK) return prc;
+    }
+    if (pp || q.best_k || q.best_action || q.best_ret) {
+        hipLaunchKernelGGL(sequences_combine_kernel, dim3((unsigned)((q.M + 3) / 4)), dim3(256), 0, st, q, p.track_id);
+        HIPCHK(hipGetLastError());
+    }
+    return PC_OK;
+}
+
+// what the value form adds to sequences_args: refused before the handles are looked at, else filled into q
+static int sequences_value_args(SequencesValue& q, double gamma, int bootstrap, const pc_policy* pp, const float* image, void* workspace,
+                                float* end_obs, float* end_value, double* end_discount, double* ret_env) {
+    if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return PC_ERR_INVALID_ARG;
+    if (bootstrap != PC_SEQ_BOOTSTRAP_NONE && bootstrap != PC_SEQ_BOOTSTRAP_RUNNING && bootstrap != PC_SEQ_BOOTSTRAP_RUNNING_TRUNCATED)
+        return PC_ERR_INVALID_ARG;
+    if ((pp == nullptr) != (image == nullptr)) return PC_ERR_INVALID_ARG;
+    if (bootstrap != PC_SEQ_BOOTSTRAP_NONE && !pp) return PC_ERR_INVALID_ARG;
+    if (pp && (!end_obs || !end_value || !workspace)) return PC_ERR_INVALID_ARG;
+    q.gamma = gamma; q.bootstrap = bootstrap;
+    q.end_obs = end_obs; q.end_value = pp ? end_value : nullptr; q.end_discount = end_discount; q.ret_env = ret_env;
+    return PC_OK;
+}
+
+extern "C" {
+
+int64_t pc_env_rollout_sequences_value_workspace(int64_t M, int K) {
+    if (M < 1 || K < 1 || K > PC_SEQ_MAX_CANDIDATES) return 0;
+    return sequences_value_ws_bytes(M, K);
+}
+
+int pc_env_rollout_sequences_value(const pc_env* e, const double* px, const double* py, const double* vx, const double* vy, const int32_t* turns,
+                                   const int32_t* next_gate, const int32_t* time_step, const uint8_t* track_id, const uint8_t* active, int64_t M,
+                                   const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale, double gamma,
+                                   int bootstrap, const pc_policy* p, const float* image, void* workspace, double* ret, int32_t* steps,
+                                   uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k, int64_t* best_action, double* best_ret,
+                                   float* end_obs, float* end_value, double* end_discount, double* ret_env, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;      // (this and the refusals below come before the handles are looked at)
+    if (!px || !py || !vx || !vy || !turns || M < 1) return PC_ERR_INVALID_ARG;
+    SequencesValue q{};
+    int rc = sequences_args(q, actions, actions_state_stride, K, H, reward_scale, ret, steps, status, gates, laps, best_k, best_action, best_ret);
+    if (rc == PC_OK) rc = sequences_value_args(q, gamma, bootstrap, p, image, workspace, end_obs, end_value, end_discount, ret_env);
+    if (rc != PC_OK) return rc;
+    if (p && (p->D != e->D || p->device != e->device)) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    static_cast<PoseRows&>(q) = pose_rows<false>(e, px, py, vx, vy, turns, next_gate, time_step, track_id, active, M);
+    return by_dtype(e, [&](auto t) { return sequences_value_launch<decltype(t)>(e, q, p, image, workspace, end_value, (hipStream_t)stream); });
+}
+
+int pc_env_rollout_sequences_value_state(pc_env* e, const uint8_t* actions, int64_t actions_state_stride, int K, int H, double reward_scale,
+                                         double gamma, int bootstrap, const pc_policy* p, const float* image, void* workspace, double* ret,
+                                         int32_t* steps, uint8_t* status, int32_t* gates, int32_t* laps, int32_t* best_k, int64_t* best_action,
+                                         double* best_ret, float* end_obs, float* end_value, double* end_discount, double* ret_env,
+                                         void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!e) return PC_ERR_INVALID_ARG;
+    SequencesValue q{};
+    int rc = sequences_args(q, actions, actions_state_stride, K, H, reward_scale, ret, steps, status, gates, laps, best_k, best_action, best_ret);
+    if (rc == PC_OK) rc = sequences_value_args(q, gamma, bootstrap, p, image, workspace, end_obs, end_value, end_discount, ret_env);
+    if (rc != PC_OK) return rc;
+    if (p && (p->D != e->D || p->device != e->device)) return PC_ERR_INVALID_ARG;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    static_cast<PoseRows&>(q) = state_rows(e);
+    return by_dtype(e, [&](auto t) { return sequences_value_launch<decltype(t)>(e, q, p, image, workspace, end_value, (hipStream_t)stream); });
 }
 
 int pc_ppo_gather(int device, const int64_t* idx, int B, int D, const float* obs, const float* act, const float* logprob,

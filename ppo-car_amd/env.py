@@ -136,6 +136,7 @@ class VecCarEnv:
         self._tracks = None
         self._track_id = None if track_id is None else np.ascontiguousarray(track_id, np.uint8)
         self._opts = {}
+        self._seq_ws = None      # the policy step's side outputs in rollout_sequences(agent=...), grown on demand
         self._build(tracks)
         self._episodes = None
         if record_episode_statistics:
@@ -387,8 +388,11 @@ class VecCarEnv:
                 ("laps", torch.int32, True), ("best_k", torch.int32, False), ("best_action", torch.int64, False),
                 ("best_ret", torch.float64, False))
 
-    def _sequence_args(self, what, M, actions, reward_scale, out):
-        """(the call's trailing arguments from `actions` on, the dict to return)"""
+    _SEQ_VALUE_OUT = (("end_obs", torch.float32), ("end_value", torch.float32), ("end_discount", torch.float64), ("ret_env", torch.float64))
+
+    def _sequence_args(self, what, M, actions, reward_scale, out, value=None):
+        """(the call's trailing arguments from `actions` on, the dict to return).  value: None, or (gamma, bootstrap, agent, repack) for
+        the entry points that discount and bootstrap (pc_env_rollout_sequences_value[_state])."""
         if actions.dtype != torch.uint8 or actions.dim() not in (2, 3) or (actions.dim() == 3 and actions.shape[0] != M):
             raise ValueError(f"{what}: actions must be a uint8 tensor [H, K] (shared) or [{M}, H, K] (per state), got "
                              f"{tuple(actions.shape)} {actions.dtype}")
@@ -402,11 +406,43 @@ class VecCarEnv:
                 res[name] = out.get(name)      # an `out` without an optional key: that array is not asked for
         ptrs = [self._ptr(res[name], dtype, M * K if per_lane else M, name) for name, dtype, per_lane in self._SEQ_OUT]
         scale = self.reward_scaling if reward_scale is None else float(reward_scale)
-        args = [self._ptr(actions, torch.uint8, actions.numel(), "actions"), stride, K, H, scale] + ptrs + [self._stream()]
+        args = [self._ptr(actions, torch.uint8, actions.numel(), "actions"), stride, K, H, scale]
+        if value is not None:
+            gamma, bootstrap, agent, repack = value
+            gamma = 1.0 if gamma is None else float(gamma)
+            mode = _capi.SEQ_BOOTSTRAP.get("none" if bootstrap is None else bootstrap, bootstrap)
+            if not isinstance(mode, int):
+                raise ValueError(f"{what}: bootstrap must be one of {sorted(_capi.SEQ_BOOTSTRAP)}, not {bootstrap!r}")
+            handle = image = ws = None
+            if agent is not None:
+                handle = agent._policy_handle() if agent._std_mlp() else None
+                stale = not getattr(agent, "_image_ok", False) or getattr(agent, "_image_handle", None) is not handle
+                if handle is None or ((repack or stale) and not agent.pack_policy()):
+                    raise ValueError(f"{what}: the agent's shape is outside the fused policy step's menu (two 1-hidden-layer MLPs of 256 "
+                                     "units, obs dim <= 40, <= 15 actions); there is no torch fallback for the critic here")
+                image = agent._image.data_ptr()
+                nbytes = lib.pc_env_rollout_sequences_value_workspace(M, K)
+                if self._seq_ws is None or self._seq_ws.numel() < nbytes:
+                    self._seq_ws = self._new(max(nbytes, 16), dtype=torch.uint8)
+                ws = self._seq_ws.data_ptr()
+            D = self.obs_dim
+            for name, dtype in self._SEQ_VALUE_OUT:
+                need = agent is not None and name in ("end_obs", "end_value")
+                if name == "end_value" and agent is None:
+                    res[name] = None      # (no policy: nothing would be written)
+                elif (out is None) or (need and name not in out):
+                    res[name] = self._new(M, K, D, dtype=dtype) if name == "end_obs" else self._new(M, K, dtype=dtype)
+                else:
+                    res[name] = out.get(name)
+            args += [gamma, mode, handle, image, ws] + ptrs
+            args += [self._ptr(res[name], dtype, M * K * (D if name == "end_obs" else 1), name) for name, dtype in self._SEQ_VALUE_OUT]
+        else:
+            args += ptrs
+        args.append(self._stream())
         return args, {k: v for k, v in res.items() if v is not None}
 
     def rollout_sequences(self, px, py, vx, vy, turns, actions, next_gate=None, time_step=None, track_id=None, active=None,
-                          reward_scale=None, out=None):
+                          reward_scale=None, out=None, gamma=None, bootstrap=None, agent=None, repack=True):
         """What each of K action sequences of H steps earns from each of M states (step = step_poses' step; a sequence that terminated
         or truncated takes no further step).  px, py, vx, vy float64, turns int32 (observe_poses' heading rule), next_gate / time_step
         int32 (default 0), track_id uint8 (default track 0), active uint8 (default every row; a row with 0 is not written in any
@@ -415,17 +451,32 @@ class VecCarEnv:
         tensors: ret float64, steps int32, status uint8 (_capi.PC_FIRST_*), gates, laps int32, each [M, K]; best_k int32 (the lowest k
         of the row's maximum), best_action int64 (its first action), best_ret float64, each [M].  out: a dict of tensors to fill; with
         `out` given, an optional key it lacks (gates, laps, best_*) is not computed.  A row whose track_id this env does not have gets
-        zeros (best_action 8).  The env state is neither read nor written; no synchronisation."""
+        zeros (best_action 8).  The env state is neither read nor written; no synchronisation.
+        gamma, bootstrap, agent: all None (the default) is the call above.  Otherwise pc_env_rollout_sequences_value: ret is the
+        discounted sum (gamma, default 1.0) plus, where `bootstrap` ("none", "running" or "running_truncated") covers the lane's status,
+        end_discount * the value `agent`'s critic gives the observation the lane ends at -- one fused policy step over all M * K end
+        observations.  agent: a ppo_car_amd.Agent on the fused menu (a ValueError otherwise: there is no torch fallback); its weights
+        are packed once per call unless repack=False.  The dict gains end_obs float32 [M, K, D], end_value float32 (with an agent),
+        end_discount and ret_env float64 [M, K]; with `out` given, end_discount / ret_env (and, without an agent, end_obs) are computed
+        only where `out` has the key."""
         M, rows = self._pose_args("rollout_sequences", px, py, vx, vy, turns, next_gate=next_gate, time_step=time_step, track_id=track_id,
                                   active=active)
-        args, res = self._sequence_args("rollout_sequences", M, actions, reward_scale, out)
-        check(lib.pc_env_rollout_sequences(self._h, *rows, M, *args), "pc_env_rollout_sequences")
+        if gamma is None and bootstrap is None and agent is None:
+            args, res = self._sequence_args("rollout_sequences", M, actions, reward_scale, out)
+            check(lib.pc_env_rollout_sequences(self._h, *rows, M, *args), "pc_env_rollout_sequences")
+            return res
+        args, res = self._sequence_args("rollout_sequences", M, actions, reward_scale, out, (gamma, bootstrap, agent, repack))
+        check(lib.pc_env_rollout_sequences_value(self._h, *rows, M, *args), "pc_env_rollout_sequences_value")
         return res
 
-    def score_sequences(self, actions, reward_scale=None, out=None):
+    def score_sequences(self, actions, reward_scale=None, out=None, gamma=None, bootstrap=None, agent=None, repack=True):
         """rollout_sequences() of every env's CURRENT state, as step() holds it (M = n_envs).  The state is not modified."""
-        args, res = self._sequence_args("score_sequences", self.num_envs, actions, reward_scale, out)
-        check(lib.pc_env_rollout_sequences_state(self._h, *args), "pc_env_rollout_sequences_state")
+        if gamma is None and bootstrap is None and agent is None:
+            args, res = self._sequence_args("score_sequences", self.num_envs, actions, reward_scale, out)
+            check(lib.pc_env_rollout_sequences_state(self._h, *args), "pc_env_rollout_sequences_state")
+            return res
+        args, res = self._sequence_args("score_sequences", self.num_envs, actions, reward_scale, out, (gamma, bootstrap, agent, repack))
+        check(lib.pc_env_rollout_sequences_value_state(self._h, *args), "pc_env_rollout_sequences_value_state")
         return res
 
     def render(self, envs=None, scale=2):

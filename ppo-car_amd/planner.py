@@ -15,24 +15,54 @@ of: pc_cem_sample (K23) draws that env's K sequences from ITS weights, K22 score
 the round before in column 9, so an env's best return never falls from one round to the next.  With warm_start the weights are carried
 from one real step to the next, shifted by one step.  All integer: a host can reproduce every table (tests/cem_reference.py).
 
+Both planners take agent=None, gamma=1.0, bootstrap="none": with an agent and bootstrap "running" or "running_truncated" a sequence
+is scored by its discounted return plus gamma^n * the agent's critic at the state it ends in (pc_env_rollout_sequences_value: K25, the
+fused policy step, K26), so a short horizon sees what a long one would; CEM then refits on those returns.  The agent's weights are packed
+once per act() / plan().  The defaults make the calls, and give the bits, the planners always did.
+
 PlannerEvaluator is the Evaluator's counterpart for the planner: the first episodes of N fresh envs, PC_TIME_LIMIT steps of act() +
 pc_env_step, pc_first_episodes over windows, reported through evaluation_scalars -- the same eval/* keys a policy evaluation prints, so
 a trained policy's lap and crash figures have something to stand beside."""
 import torch
 
-from ._capi import PC_CEM_MAX_HORIZON, PC_CEM_W_MAX, PC_EPISODE_STEPS, PC_SEQ_MAX_CANDIDATES, PC_TIME_LIMIT, check, lib
+from ._capi import SEQ_BOOTSTRAP, PC_CEM_MAX_HORIZON, PC_CEM_W_MAX, PC_EPISODE_STEPS, PC_SEQ_MAX_CANDIDATES, PC_TIME_LIMIT, check, lib
 from .env import VecCarEnv
 from .evaluation import evaluation_scalars, new_state, state_totals
 
 N_ACTIONS = 9
 
 
+def _critic_args(who, envs, agent, gamma, bootstrap):
+    """The scoring call's extra keywords for a planner: {} for the defaults (the call without a discount, today's bits), else gamma,
+    bootstrap and agent for score_sequences / rollout_sequences -- and, for the planner's `out`, the arrays that call requires."""
+    if bootstrap not in SEQ_BOOTSTRAP:
+        raise ValueError(f"{who}: bootstrap must be one of {sorted(SEQ_BOOTSTRAP)}, not {bootstrap!r}")
+    gamma = float(gamma)
+    if not 0.0 <= gamma <= 1.0:      # (NaN fails both comparisons)
+        raise ValueError(f"{who}: gamma must be in 0 .. 1, not {gamma!r}")
+    if bootstrap != "none" and agent is None:
+        raise ValueError(f"{who}: bootstrap={bootstrap!r} needs an agent (its critic values the end states)")
+    if agent is None and gamma == 1.0:
+        return {}
+    return dict(gamma=gamma, bootstrap=bootstrap, agent=agent)
+
+
+def _critic_out(kw, envs, M, K):
+    """the tensors the value form fills beside K22's, for a planner's `out` dict"""
+    if not kw or kw["agent"] is None:
+        return {}
+    dev = envs.device
+    return dict(end_obs=torch.empty(M, K, envs.obs_dim, dtype=torch.float32, device=dev),
+                end_value=torch.empty(M, K, dtype=torch.float32, device=dev))
+
+
 class Planner:
-    def __init__(self, envs, horizon=16, candidates=256, seed=0):
+    def __init__(self, envs, horizon=16, candidates=256, seed=0, agent=None, gamma=1.0, bootstrap="none"):
         if not 1 <= int(horizon) <= PC_TIME_LIMIT:
             raise ValueError(f"Planner: horizon must be 1 .. {PC_TIME_LIMIT}, not {horizon!r}")
         if not N_ACTIONS <= int(candidates) <= PC_SEQ_MAX_CANDIDATES:
             raise ValueError(f"Planner: candidates must be {N_ACTIONS} (the constant sequences) .. {PC_SEQ_MAX_CANDIDATES}, not {candidates!r}")
+        self._critic = _critic_args("Planner", envs, agent, gamma, bootstrap)
         self.envs, self.horizon, self.candidates, self.seed = envs, int(horizon), int(candidates), int(seed)
         dev, N, H, K = envs.device, envs.num_envs, self.horizon, self.candidates
         self.device = dev
@@ -45,6 +75,7 @@ class Planner:
         self.out = dict(ret=torch.empty(N, K, dtype=torch.float64, device=dev), steps=torch.empty(N, K, dtype=torch.int32, device=dev),
                         status=torch.empty(N, K, dtype=torch.uint8, device=dev), best_k=torch.empty(N, dtype=torch.int32, device=dev),
                         best_action=torch.empty(N, dtype=torch.int64, device=dev), best_ret=torch.empty(N, dtype=torch.float64, device=dev))
+        self.out.update(_critic_out(self._critic, envs, N, K))
 
     def candidate_table(self, step_index):
         """The shared table of this step, uint8 [H, K] on the device (self.table, overwritten by every call)."""
@@ -58,7 +89,7 @@ class Planner:
     def act(self, step_index):
         """int64 [N]: the first action of each env's best candidate from its current state (self.out["best_action"], overwritten by
         every call).  The env state is not modified; no host synchronisation."""
-        self.envs.score_sequences(self.candidate_table(step_index), out=self.out)
+        self.envs.score_sequences(self.candidate_table(step_index), out=self.out, **self._critic)      # (an agent is packed here, once)
         return self.out["best_action"]
 
     def drive(self, n_steps, start=0, out=None):
@@ -78,7 +109,7 @@ class CEMPlanner:
     STATE_KEYS = ("px", "py", "vx", "vy", "turns")      # of plan(states=...): required; next_gate, time_step, track_id, active optional
 
     def __init__(self, envs, horizon=16, candidates=64, elites=8, iterations=4, smoothing_shift=1, min_weight=64, init_weight=7281,
-                 warm_start=True, seed=0):
+                 warm_start=True, seed=0, agent=None, gamma=1.0, bootstrap="none"):
         if not 1 <= int(horizon) <= PC_CEM_MAX_HORIZON:
             raise ValueError(f"CEMPlanner: horizon must be 1 .. {PC_CEM_MAX_HORIZON}, not {horizon!r}")
         if not N_ACTIONS + 1 <= int(candidates) <= PC_SEQ_MAX_CANDIDATES:
@@ -97,6 +128,7 @@ class CEMPlanner:
         self.envs, self.horizon, self.candidates, self.elites = envs, int(horizon), int(candidates), int(elites)
         self.iterations, self.smoothing_shift, self.min_weight = int(iterations), int(smoothing_shift), int(min_weight)
         self.init_weight, self.warm_start, self.seed = int(init_weight), bool(warm_start), int(seed)
+        self._critic = _critic_args("CEMPlanner", envs, agent, gamma, bootstrap)
         self.device = envs.device
         self.weights = self.table = self.best_seq = self.out = self.iter_best_ret = None
         self._rows(envs.num_envs)
@@ -114,6 +146,7 @@ class CEMPlanner:
         self.out = dict(ret=torch.empty(M, K, dtype=torch.float64, device=dev), steps=torch.empty(M, K, dtype=torch.int32, device=dev),
                         status=torch.empty(M, K, dtype=torch.uint8, device=dev), best_k=torch.empty(M, dtype=torch.int32, device=dev),
                         best_action=torch.empty(M, dtype=torch.int64, device=dev), best_ret=torch.empty(M, dtype=torch.float64, device=dev))
+        self.out.update(_critic_out(self._critic, self.envs, M, K))
 
     def reset_plan(self):
         """Every state's weights back to init_weight: the plan of a planner just made."""
@@ -155,12 +188,13 @@ class CEMPlanner:
         for i in range(self.iterations):
             check(lib.pc_cem_sample(dev.index, self.weights.data_ptr(), M, H, K, self.seed, int(step_index) * self.iterations + i, 1,
                                     self.best_seq.data_ptr() if i > 0 else None, act_ptr, self.table.data_ptr(), stream), "pc_cem_sample")
+            kw = dict(self._critic, repack=i == 0) if self._critic else {}      # (the agent's image: packed once per plan, not per round)
             if states is None:
-                self.envs.score_sequences(self.table, out=self.out)
+                self.envs.score_sequences(self.table, out=self.out, **kw)
             else:
                 self.envs.rollout_sequences(states["px"], states["py"], states["vx"], states["vy"], states["turns"], self.table,
                                             next_gate=states.get("next_gate"), time_step=states.get("time_step"),
-                                            track_id=states.get("track_id"), active=active, out=self.out)
+                                            track_id=states.get("track_id"), active=active, out=self.out, **kw)
             self.iter_best_ret[i].copy_(self.out["best_ret"])
             check(lib.pc_cem_refit(dev.index, self.weights.data_ptr(), self.out["ret"].data_ptr(), self.table.data_ptr(), M, H, K,
                                    self.elites, self.smoothing_shift, self.min_weight, act_ptr, self.best_seq.data_ptr(), stream),
@@ -191,7 +225,7 @@ class PlannerEvaluator:
 
     def __init__(self, tracks, n_envs=1024, num_rays=12, reward_scaling=0.1, device="cuda", dtype="f32", track_id=None, horizon=16,
                  candidates=256, seed=0, chunk=250, kind="shooting", elites=8, iterations=4, smoothing_shift=1, min_weight=64,
-                 init_weight=7281, warm_start=True):
+                 init_weight=7281, warm_start=True, agent=None, gamma=1.0, bootstrap="none"):
         if kind not in ("shooting", "cem"):
             raise ValueError(f"PlannerEvaluator: kind must be 'shooting' or 'cem', not {kind!r}")
         if int(n_envs) < 1:
@@ -204,9 +238,9 @@ class PlannerEvaluator:
         try:
             if kind == "cem":
                 self.planner = CEMPlanner(self.envs, horizon, candidates, elites, iterations, smoothing_shift, min_weight, init_weight,
-                                          warm_start, seed)
+                                          warm_start, seed, agent=agent, gamma=gamma, bootstrap=bootstrap)
             else:
-                self.planner = Planner(self.envs, horizon, candidates, seed)
+                self.planner = Planner(self.envs, horizon, candidates, seed, agent=agent, gamma=gamma, bootstrap=bootstrap)
         except Exception:
             self.envs.close()
             raise
