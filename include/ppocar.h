@@ -747,7 +747,28 @@ int pc_ppo_minibatch(int device, const int64_t* idx, int B, int D, int H, int A,
                      double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
                      void* stream);
 
-/* The same step on a minibatch gathered beforehand.  pc_ppo_prepare gathers n_mb minibatches in ONE launch: minibatch m
+/* ---- one supervised minibatch step on the same flat buckets (behaviour cloning of a teacher's actions; K27, then the reduction
+ * and clip + Adam launches of pc_ppo_minibatch unchanged): gather, both MLPs forward, the loss below, both MLPs backward, and
+ * (apply == 1) clip_grad_norm_ + Adam.  No library GEMM, no atomics, a fixed summation order: two calls give the same bits.
+ *   obs [M][D]; label [M] float32 (act_buf's layout: a rollout buffer's actions can serve); target [M] float32, the critic's
+ *   regression targets, or NULL; idx [B] int64 into them, duplicates allowed.
+ *   With labelled_i = (0 <= label_i < A):
+ *     ce_i  = labelled_i ? -log_softmax(logits_i)[label_i] : 0      ent_i = labelled_i ? entropy(softmax(logits_i)) : 0
+ *     vl_i  = 0.5 (v_i - target_i)^2
+ *     loss  = (sum_i ce_i + vf_coef * sum_i vl_i - ent_coef * sum_i ent_i) / B
+ *   The divisor is always B.  A label outside 0 .. A-1 means "no label" (the planners' doomed states carry -1): the actor's
+ *   gradient of that sample is exactly zero and it adds nothing to the ce and ent sums; its value term still counts.
+ *   target == NULL needs vf_coef == 0 (PC_ERR_INVALID_ARG otherwise): the critic's gradient is +0.0f in every element, metrics[1]
+ *   gets +0, and a clip + Adam step from zero moments leaves the critic's parameters bit-identical.
+ * metrics[4] += (mean ce, mean vl, mean ent, total); grad receives the (clipped, when applied) gradient; apply 0 / 1 / 2,
+ * step_count, lr_dev, the workspace (pc_ppo_workspace_floats(B, D, H, A) floats), the limits (H == 256, A <= 15, D <= 40,
+ * 2 <= B <= 1024: PC_ERR_UNSUPPORTED) and the order of the checks (those that need no device first) are pc_ppo_minibatch's. */
+int pc_bc_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* label,
+                    const float* target, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count,
+                    const float* lr_dev, double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps,
+                    float* metrics, float* workspace, int apply, void* stream);
+
+/* The same step on a minibatch gathered beforehand. pc_ppo_prepare gathers n_mb minibatches in ONE launch: minibatch m
  * reads its B indices at idx[m * idx_ld ...] and writes, at prepared + m * pc_ppo_prepared_floats(B, D), the sample rows
  * obs[idx] [B][D], then act / old_logprob / adv / ret [B] each, then (mean, max(unbiased std, 1e-5)) of its advantages and
  * two pad floats -- what every workgroup of pc_ppo_minibatch otherwise fetches (an index load, then the dependent row

@@ -140,7 +140,8 @@ _sig = {
     "pc_ppo_epoch_state_floats": (_i64, [_i, _i, _i]),
     "pc_ppo_epoch_prepared": (_i, [_i, _vp, _i, _i, _i, _i, _i] + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _vp, _vp]),
     "pc_ppo_minibatch": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 5 + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp]),
-    "pc_ppo_large_workspace_floats": (_i64, [_i, _i, _i, _i, _i]),
+    "pc_bc_minibatch": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 3 + [_vp] * 6 + [_d] * 6 + [_vp, _vp, _i, _vp]),
+    "pc_ppo_large_workspace_floats":(_i64, [_i, _i, _i, _i, _i]),
     "pc_ppo_large_parts": (_i, [_i, _i]),
     "pc_ppo_adv_stats_workspace_doubles": (_i64, [_i, _i]),
     "pc_ppo_adv_stats": (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),

@@ -316,7 +316,13 @@ __global__ __launch_bounds__(256) void ppo_prepare_kernel(const int64_t* __restr
 // DC > 0: likewise the observation width (6 + 12 / 17 / 33 rays).
 // DIAG: the update-diagnostics form (ppo_loss_body's comment): the stop flag is read first, and each workgroup also leaves the sums of
 // its samples' KL terms and clipped-sample counts in diag_partial[wg][2] -- a second partial: (pl, vl, ent, -) keeps its layout.
-template <int DMAX, int AC = 0, int DC = 0, bool DEFER = false, bool DIAG = false>
+// LOSS: the loss section's head.  LOSS_PPO: the clipped surrogate.  LOSS_BC (K27, pc_bc_minibatch): cross-entropy against a label --
+// `act` holds the labels (outside 0 .. A-1: no label, the actor's lanes and the sample's ce / ent are exactly 0), `ret` the critic's
+// targets (nullptr: no value term, the value lane is exactly +0), old_lp / adv are not read and no advantage statistics are reduced;
+// (ce, vl, ent) take (pl, vl, ent)'s places in the metric partial.  The value lane, the entropy and everything outside the loss
+// section are the same statements for both.
+constexpr int LOSS_PPO = 0, LOSS_BC = 1;
+template <int DMAX, int AC = 0, int DC = 0, bool DEFER = false, bool DIAG = false, int LOSS = LOSS_PPO>
 __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __restrict__ idx, const int B, const int D_rt, const int A_rt,
                                                 const float* __restrict__ obs, const float* __restrict__ act,
                                                 const float* __restrict__ old_lp, const float* __restrict__ adv,
@@ -327,6 +333,7 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
                                                 const float* __restrict__ diag = nullptr, float* __restrict__ diag_partial = nullptr) {
     constexpr int H = 256, S = FB_S, LDT = DMAX + 1, LDH = H + 1;
     static_assert(!(DIAG && DEFER), "the deferred chain has no diagnostics form");
+    static_assert(LOSS == LOSS_PPO || !(DIAG || DEFER), "the cross-entropy step has neither a diagnostics nor a deferred form");
     if constexpr (DIAG) if (diag[4] != 0.0f) return;   // (uniform) the epoch's update has stopped: this launch costs its latency only
     const int A = AC > 0 ? AC : A_rt, D = DC > 0 ? DC : D_rt;
     static_assert(DC <= DMAX, "observation width");
@@ -360,7 +367,7 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
     if (!prep) {
         if (u < S && s0 + u < B) my_src = idx[s0 + u];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) a_src[j] = u + j * 256 < B ? idx[u + j * 256] : 0;
+        for (int j = 0; j < 4; ++j) a_src[j] = LOSS == LOSS_PPO && u + j * 256 < B ? idx[u + j * 256] : 0;
     }
     // defer (uniform): `param` holds generation i, the previous minibatch's clip + Adam step has not been taken yet (AdamDefer):
     // every parameter element this thread loads is loaded with its gradient and moments, updated in registers, and -- by
@@ -498,15 +505,20 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            a_loc[j] = u + j * 256 < B ? adv[a_src[j]] : 0.0f;
+            a_loc[j] = LOSS == LOSS_PPO && u + j * 256 < B ? adv[a_src[j]] : 0.0f;
             a_sum += a_loc[j];
         }
         if (u < S) {
             const bool lv = s0 + u < B;
             sSmp[u][0] = lv ? act[my_src] : 0.0f;
-            sSmp[u][1] = lv ? old_lp[my_src] : 0.0f;
-            sSmp[u][2] = lv ? adv[my_src] : 0.0f;
-            sSmp[u][3] = lv ? ret[my_src] : 0.0f;
+            if constexpr (LOSS == LOSS_PPO) {
+                sSmp[u][1] = lv ? old_lp[my_src] : 0.0f;
+                sSmp[u][2] = lv ? adv[my_src] : 0.0f;
+                sSmp[u][3] = lv ? ret[my_src] : 0.0f;
+            } else {
+                sSmp[u][1] = sSmp[u][2] = 0.0f;
+                sSmp[u][3] = lv && ret ? ret[my_src] : 0.0f;      // (uniform: with or without targets)
+            }
         }
         for (int i = u; i < S * DMAX; i += 256) {                         // gather my workgroup's samples (train.py:233-238)
             const int sidx = i / DMAX, f = i - sidx * DMAX;
@@ -537,7 +549,7 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
     // ---- per-minibatch advantage statistics (train.py:238-240), recomputed identically by every workgroup
     const float invB = 1.0f / (float)B;
     float mean = pre_mean, sd = pre_sd;
-    if (!prep) adv_stats(a_loc, a_sum, B, sh, mean, sd);   // (uniform branch)
+    if constexpr (LOSS == LOSS_PPO) if (!prep) adv_stats(a_loc, a_sum, B, sh, mean, sd);   // (uniform branch)
     __syncthreads();   // (also: every thread has read its W1 row out of the tile, which sHid / sW2 alias)
 
     PC_STAMP_U(2)
@@ -632,19 +644,35 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
         ent += PC_ROW_ROR(ent, 4);
         ent += PC_ROW_ROR(ent, 2);
         ent += PC_ROW_ROR(ent, 1);
-        const int a = (int)sSmp[sidx][0];
-        const float new_lp = __shfl(lpk, (u & 48) + (a & 15), 64);            // the row's lane a
-        const float r = expf(new_lp - sSmp[sidx][1]);                         // :235
-        const float An = (sSmp[sidx][2] - mean) / sd;                         // :238-240
-        const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
-        const float pl1 = -An * r, pl2 = -An * rc;                            // :243-244
-        const float pl = fmaxf(pl1, pl2);                                     // :245
-        const float dv = __shfl(o, (u & 48) + A, 64) - sSmp[sidx][3];
-        const float vl = 0.5f * dv * dv;                                      // :249
-        const float g_lp = (pl1 >= pl2 ? -An : 0.0f) * r * invB;
-        float dk = 0.0f;
-        if (k < A) dk = g_lp * ((k == a ? 1.0f : 0.0f) - pk) + ec * invB * pk * (lpk + ent);
-        else if (k == A) dk = vf * dv * invB;
+        float pl, vl, dk = 0.0f;
+        [[maybe_unused]] float r = 0.0f, new_lp = 0.0f;
+        if constexpr (LOSS == LOSS_PPO) {
+            const int a = (int)sSmp[sidx][0];
+            new_lp = __shfl(lpk, (u & 48) + (a & 15), 64);                    // the row's lane a
+            r = expf(new_lp - sSmp[sidx][1]);                                 // :235
+            const float An = (sSmp[sidx][2] - mean) / sd;                     // :238-240
+            const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
+            const float pl1 = -An * r, pl2 = -An * rc;                        // :243-244
+            pl = fmaxf(pl1, pl2);                                             // :245
+            const float dv = __shfl(o, (u & 48) + A, 64) - sSmp[sidx][3];
+            vl = 0.5f * dv * dv;                                              // :249
+            const float g_lp = (pl1 >= pl2 ? -An : 0.0f) * r * invB;
+            if (k < A) dk = g_lp * ((k == a ? 1.0f : 0.0f) - pk) + ec * invB * pk * (lpk + ent);
+            else if (k == A) dk = vf * dv * invB;
+        } else {
+            // cross-entropy against the label: pl = -log_softmax[label]; a label outside 0 .. A-1 (NaN too) is "no label"
+            const float lab = sSmp[sidx][0];
+            const bool labelled = lab >= 0.0f && lab < (float)A;
+            const int a = labelled ? (int)lab : 0;
+            new_lp = __shfl(lpk, (u & 48) + a, 64);                           // the row's lane a
+            pl = labelled ? -new_lp : 0.0f;
+            if (!labelled) ent = 0.0f;
+            const float dv = ret ? __shfl(o, (u & 48) + A, 64) - sSmp[sidx][3] : 0.0f;
+            vl = 0.5f * dv * dv;
+            const float g_lp = labelled ? -invB : 0.0f;
+            if (k < A) dk = labelled ? g_lp * ((k == a ? 1.0f : 0.0f) - pk) + ec * invB * pk * (lpk + ent) : 0.0f;
+            else if (k == A) dk = ret ? vf * dv * invB : 0.0f;
+        }
         sDout[sidx][k] = live ? dk : 0.0f;
         if (k == 0) {
             sMet[sidx][0] = live ? pl : 0.0f;
@@ -771,6 +799,17 @@ __global__ __launch_bounds__(256) void ppo_fwdbwd_diag_kernel(const int64_t* __r
                                                               float* __restrict__ diag_partial) {
     ppo_fwdbwd_body<DMAX, AC, DC, false, true>(blockIdx.x, idx, B, D, A, obs, act, old_lp, adv, ret, param, clip, vf, ec, partial, metric_partial, prep,
                                                AdamDefer{}, diag, diag_partial);
+}
+// K27: the body with the cross-entropy head (LOSS_BC): a supervised minibatch step's forward / backward launch.  label [M] float32 in
+// act_buf's layout, target [M] or nullptr; K11 and K12 follow it unchanged (the partials have K10's layout).
+template <int DMAX, int AC = 0, int DC = 0>
+__global__ __launch_bounds__(256) void bc_fwdbwd_kernel(const int64_t* __restrict__ idx, const int B, const int D, const int A,
+                                                        const float* __restrict__ obs, const float* __restrict__ label,
+                                                        const float* __restrict__ target, const float* __restrict__ param,
+                                                        const float vf, const float ec,
+                                                        float* __restrict__ partial, float* __restrict__ metric_partial) {
+    ppo_fwdbwd_body<DMAX, AC, DC, false, false, LOSS_BC>(blockIdx.x, idx, B, D, A, obs, label, nullptr, nullptr, target, param, 0.0f, vf, ec, partial,
+                                                         metric_partial, nullptr, AdamDefer{});
 }
 
 // K11: flat_grad[i] = sum_p partial[p][i] (fixed order: deterministic); block-wise squared-norm partials for the clip;

@@ -2156,7 +2156,8 @@ int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
 // One minibatch step as the entry points hand it over
 struct MbSamples {      // the rollout's tensors and this minibatch's indices, or (prep) a block ppo_prepare_kernel gathered
     const int64_t* idx; const float *obs, *act, *old_logprob, *adv, *ret, *prep;
-    bool complete() const { return prep || (idx && obs && act && old_logprob && adv && ret); }
+    bool bc = false;        // the cross-entropy step (K27): act = the labels, ret = the critic's targets or nullptr, no old_logprob / adv
+    bool complete() const { return bc ? idx && obs && act : prep || (idx && obs && act && old_logprob && adv && ret); }
 };
 struct MbState { float *param, *grad, *exp_avg, *exp_avg_sq, *step_count; const float* lr_dev; };
 struct MbCoef { double clip_ratio, vf_coef, ent_coef, max_norm, beta1, beta2, eps; };
@@ -2177,7 +2178,7 @@ static int check_apply_args(const MbStep& m) {
     return m.apply < 0 || m.apply > 2 ? PC_ERR_INVALID_ARG : PC_OK;
 }
 
-// K10 (its diagnostics form with `diag`, its deferred form with df.grad) on `param`
+// K10 (its diagnostics form with `diag`, its deferred form with df.grad; K27 with in.bc) on `param`
 static void launch_fwdbwd(const MbPlan& pl, int B, int D, int A, const MbSamples& in, const float* param, const MbCoef& c, const AdamDefer& df,
                           const float* diag, hipStream_t st) {
     with_mlp_shape(D, A, [&](auto dm, auto ac, auto dc) {
@@ -2186,6 +2187,11 @@ static void launch_fwdbwd(const MbPlan& pl, int B, int D, int A, const MbSamples
             hipLaunchKernelGGL(kernel, dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.old_logprob, in.adv, in.ret, param,
                                (float)c.clip_ratio, (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial, in.prep, extra...);
         };
+        if (in.bc) {
+            hipLaunchKernelGGL((bc_fwdbwd_kernel<DM, AC, DC>), dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.ret, param,
+                               (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial);
+            return;
+        }
         if (diag) return go(ppo_fwdbwd_diag_kernel<DM, AC, DC>, diag, pl.diag_partial);
         if constexpr (AC > 0) if (df.grad) return go(ppo_fwdbwd_kernel<DM, AC, DC, true>, df);
         go(ppo_fwdbwd_kernel<DM, AC, DC, false>, df);
@@ -2222,7 +2228,7 @@ static int ppo_minibatch_impl(int device, int B, int D, int H, int A, const MbSt
     if (const int rc = check_apply_args(m); rc != PC_OK || !m.in.complete()) return PC_ERR_INVALID_ARG;
     if (!mlp_shape_ok(D, H, A) || !small_batch(B)) return PC_ERR_UNSUPPORTED;
     if (m.diag && m.apply == 2) return PC_ERR_UNSUPPORTED;      // (the ranks of a multi-rank step would have to agree on the stop)
-    if (m.diag && device < 0) return PC_ERR_NO_DEVICE;
+    if ((m.diag || m.in.bc) && device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const MbPlan pl(B, D, H, A, m.workspace);
@@ -2250,6 +2256,17 @@ int pc_ppo_minibatch_diag(int device, const int64_t* idx, int B, int D, int H, i
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!diag) return PC_ERR_INVALID_ARG;
     return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, act, old_logprob, adv, ret, nullptr}), diag, target_kl), stream);
+}
+
+// K27 + K11 + K12: one supervised minibatch step (cross-entropy against labels, optionally the critic's regression)
+int pc_bc_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* label, const float* target,
+                    float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double vf_coef,
+                    double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
+                    void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!target && vf_coef != 0.0) return PC_ERR_INVALID_ARG;      // (NaN too: a value term needs its targets)
+    const double clip_ratio = 0.0;                                 // (the cross-entropy head has no clip)
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, label, nullptr, nullptr, target, nullptr, true})), stream);
 }
 
 int64_t pc_ppo_prepared_floats(int B, int D) {
