@@ -7,19 +7,13 @@ import pytest
 import torch
 
 import ppo_car_amd as pc
-from ppo_car_amd import _capi
 from ppo_car_amd.imitation import BCLearner, PlannerDistiller, bc_loss
 from conftest import ROOT
+from ppo_update_reference import EC, LR, MAX_NORM, VF, Call
 
 pytestmark = pytest.mark.gpu
-lib = _capi.lib
 TRACK = os.path.join(ROOT, "tracks", "big_track.json")
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-VF, EC, MAX_NORM, LR = 0.5, 0.01, 0.5, 3e-4
-
-
-def _n_param(D, A):
-    return 2 * (256 * D + 256) + A * 256 + A + 256 + 1
 
 
 def _critic_offset(D, A):
@@ -55,41 +49,6 @@ def _batch(B, D, A, seed=0):
         idx[:2] = torch.tensor([0, 2])
         label[0], label[2] = -1.0, A - 1.0
     return obs, label, target, idx
-
-
-class Call:
-    """one pc_bc_minibatch / pc_ppo_minibatch call's device state"""
-
-    def __init__(self, param, B, D, A):
-        n = param.numel()
-        assert n == _n_param(D, A)
-        self.B, self.D, self.A = B, D, A
-        self.param = param.clone()
-        self.grad = torch.full((n,), 7.0, device="cuda")
-        self.m, self.v = torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
-        self.step = torch.zeros(1, device="cuda")
-        self.lr = torch.full((1,), LR, device="cuda")
-        self.metrics = torch.zeros(4, device="cuda")
-        self.ws = torch.zeros(lib.pc_ppo_workspace_floats(B, D, 256, A), device="cuda")
-
-    def _state(self):
-        return (self.param.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.lr.data_ptr())
-
-    def bc(self, idx, obs, label, target, vf=VF, ec=EC, apply=0):
-        _capi.check(lib.pc_bc_minibatch(0, idx.data_ptr(), self.B, self.D, 256, self.A, obs.data_ptr(), label.data_ptr(),
-                                        target.data_ptr() if target is not None else None, *self._state(), vf, ec, MAX_NORM, 0.9, 0.999, 1e-5,
-                                        self.metrics.data_ptr(), self.ws.data_ptr(), apply, torch.cuda.current_stream().cuda_stream),
-                    "pc_bc_minibatch")
-        torch.cuda.synchronize()
-        return self
-
-    def ppo(self, idx, obs, act, old_lp, adv, ret, apply=0):
-        _capi.check(lib.pc_ppo_minibatch(0, idx.data_ptr(), self.B, self.D, 256, self.A, obs.data_ptr(), act.data_ptr(), old_lp.data_ptr(),
-                                         adv.data_ptr(), ret.data_ptr(), *self._state(), 0.2, VF, EC, MAX_NORM, 0.9, 0.999, 1e-5,
-                                         self.metrics.data_ptr(), self.ws.data_ptr(), apply, torch.cuda.current_stream().cuda_stream),
-                    "pc_ppo_minibatch")
-        torch.cuda.synchronize()
-        return self
 
 
 def _cuda(*ts):
