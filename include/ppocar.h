@@ -739,6 +739,10 @@ int pc_clip_adam_advanced(int device, float* param, const float* grad, float* ex
  * the device.  apply == 0 stops after the gradient; apply == 2 stops after the gradient but advances the step counter
  * (multi-rank: all-reduce the gradient, then pc_clip_adam_advanced).  workspace: device
  * buffer of pc_ppo_workspace_floats(B, D, H, A) floats.  Deterministic (fixed summation order, no atomics).
+ * Alignment: `param` and `workspace` must be 16-byte aligned (the forward / backward launch loads the first-layer weights and
+ * stores the gradient partials as 16-byte vectors): PC_ERR_INVALID_ARG otherwise, checked with the NULL checks before any device
+ * call.  No other argument needs more than its element's alignment: idx, obs / act / old_logprob / adv / ret, grad, exp_avg,
+ * exp_avg_sq, step_count, lr_dev and metrics are read and written element by element.
  * PC_ERR_UNSUPPORTED unless H == 256, A <= 15, D <= 40, 2 <= B <= 1024. */
 int64_t pc_ppo_workspace_floats(int B, int D, int H, int A);
 int pc_ppo_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* act,
@@ -761,8 +765,9 @@ int pc_ppo_minibatch(int device, const int64_t* idx, int B, int D, int H, int A,
  *   target == NULL needs vf_coef == 0 (PC_ERR_INVALID_ARG otherwise): the critic's gradient is +0.0f in every element, metrics[1]
  *   gets +0, and a clip + Adam step from zero moments leaves the critic's parameters bit-identical.
  * metrics[4] += (mean ce, mean vl, mean ent, total); grad receives the (clipped, when applied) gradient; apply 0 / 1 / 2,
- * step_count, lr_dev, the workspace (pc_ppo_workspace_floats(B, D, H, A) floats), the limits (H == 256, A <= 15, D <= 40,
- * 2 <= B <= 1024: PC_ERR_UNSUPPORTED) and the order of the checks (those that need no device first) are pc_ppo_minibatch's. */
+ * step_count, lr_dev, the workspace (pc_ppo_workspace_floats(B, D, H, A) floats), the alignment (`param` and `workspace` 16-byte
+ * aligned: PC_ERR_INVALID_ARG; nothing else), the limits (H == 256, A <= 15, D <= 40, 2 <= B <= 1024: PC_ERR_UNSUPPORTED) and the
+ * order of the checks (those that need no device first) are pc_ppo_minibatch's. */
 int pc_bc_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* label,
                     const float* target, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count,
                     const float* lr_dev, double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps,
@@ -843,6 +848,8 @@ int pc_explained_variance(int device, const float* val, const float* ret, int64_
  *   workspace: pc_ppo_large_workspace_floats(device, B, D, H, A) floats, laid out as pc_ppo_minibatch's with `parts` partials:
  *   [parts][n_pad] gradient partials (n_pad = the parameter count rounded up to 4), [parts][4] metric partials, then the
  *   per-block squared-norm partials.  Nothing is read that the step has not written: the buffer needs no initialisation.
+ *   Alignment: as pc_ppo_minibatch, `param` and `workspace` must be 16-byte aligned (PC_ERR_INVALID_ARG, with the NULL checks);
+ *   idx, the five sample arrays, adv_stats, grad, the moments, step_count, lr_dev and metrics need their element's alignment only.
  *   Never synchronises; every launch goes to `stream`.
  * PC_ERR_UNSUPPORTED unless H == 256, 1 <= A <= 15, 1 <= D <= 40, 1024 < B <= PC_PPO_LARGE_MAX_B; PC_ERR_NO_DEVICE for device < 0
  * or a device the runtime does not know (the grid depends on the device). */

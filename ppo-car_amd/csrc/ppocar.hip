@@ -2175,6 +2175,9 @@ static int check_apply_args(const MbStep& m) {
     if (!m.s.param || !m.s.grad || !m.metrics || !m.workspace) return PC_ERR_INVALID_ARG;
     if (m.apply == 1 && (!m.s.exp_avg || !m.s.exp_avg_sq || !m.s.step_count || !m.s.lr_dev)) return PC_ERR_INVALID_ARG;
     if (m.apply == 2 && !m.s.step_count) return PC_ERR_INVALID_ARG;
+    // K10 / K10L / K27 fetch W1 out of `param` as 16-byte vectors and store the [H][D] blocks of every partial (the head of the
+    // workspace, rows of n_pad = a multiple of 4 floats) the same way: no other pointer of the step is accessed wider than 4 bytes
+    if ((((uintptr_t)m.s.param | (uintptr_t)m.workspace) & 15) != 0) return PC_ERR_INVALID_ARG;
     return m.apply < 0 || m.apply > 2 ? PC_ERR_INVALID_ARG : PC_OK;
 }
 

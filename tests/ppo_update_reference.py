@@ -1,7 +1,9 @@
 """The small-minibatch PPO step (pc_ppo_minibatch: K10 + K11 + K12) restated: the inputs of every edge-shape case, the float64 reference
 (ppo.ppo_loss on a .double() copy of the agent, clip_grad_norm_, torch.optim.Adam(lr 3e-4, eps 1e-5)) over consecutive minibatches, the
 same steps in float32 torch on the CPU (the yardstick of the input conditions; never the code under test), the two deliberately wrong
-float64 gradients of the sensitivity condition, and `Call`, one entry-point call's device state.
+float64 gradients of the sensitivity condition, and `Call`, one entry-point call's device state.  The large-minibatch step
+(pc_ppo_adv_stats + pc_ppo_minibatch_large: KLs + K10L + K11 + K12) takes the same inputs and reference at 1024 < B: its case tables
+(LARGE_*), a third wrong gradient for its walk, `adv_stats` and `Call.large`.
 
 Inputs of a case: a pool of B + 7 rows, Agent(D, A) at its seeded initial weights with actor[2] multiplied by `scale`, obs uniform in
 [-1, 1.6], old log-probs = the agent's own + 0.3 N(0, 1), adv = 3 + 0.5 N(0, 1), ret = N(0, 1), indices drawn WITH replacement, the
@@ -37,10 +39,40 @@ SEEDS = {(2, 23, 9): 2,         # 1002: no sample outside the clip range, and to
          (2, 1, 1): 1,          # 1002: no sample outside the clip range
          (256, 23, 9): 19,      # 1256: gradient norms of 0.39 .. 0.41, the norm clip at 0.5 never acts
          (1023, 40, 15): 1,     # 2023: norms of 0.24 .. 0.38
-         (65, 25, 2): 2}        # 1065: a norm of 0.495 at the third step
+         (65, 25, 2): 2,        # 1065: a norm of 0.495 at the third step
+         # the large cases (conditions of tests/test_large_minibatch_f64_host.py)
+         (2049, 39, 9): 2,      # 3049: at scale 4000 an inverted clip decision is 13 x the allowance; a ratio 8.2e-6 from an edge in the
+                                #       four idle-clip steps (seed 1: a flip that moves nothing at scale 4000)
+         (4097, 23, 9): 1,      # 5097: a ratio 4.5e-6 from a clip edge in the four idle-clip steps
+         (6151, 18, 9): 1,      # 7151: at scale 40 torch's float32 misses the gradient allowance (6.2 x); a ratio 1.7e-5 from an edge
+         (1026, 1, 15): 5,      # 2026: a gradient norm of 0.047, the norm clip at 0.05 idle in the first step (seeds 1 .. 4 likewise, or
+                                #       a ratio 2e-6 from an edge)
+         (2054, 25, 2): 3,      # 3054: at scale 4000 an inverted clip decision is 11 x the allowance (seed 1: sample 2048 dropped 8 x;
+                                #       seed 2: torch's float32 26 x the gradient allowance at scale 40)
+         (4097, 40, 15): 3}     # 5097: a ratio 4.2e-6 from a clip edge (seed 1: the last sample dropped 13 x at scale 4000; seed 2: 1e-6)
 HAND = {(B, D, A): [((0.6, 1.0, 1.45)[j % 3], 3.0 + (0.9 if (j // 3) % 2 == 0 else -0.9)) for j in range(B)]
         for B, D, A in ((7, 23, 9), (8, 23, 9), (9, 39, 9))}
 ADV_RAISED = {}         # (B, D, A, scale) -> {sample of the first minibatch: its advantage}, where the sensitivity condition needed it
+
+# ---- the large-minibatch step (pc_ppo_adv_stats + pc_ppo_minibatch_large: KLs + K10L + K11 + K12), the same inputs at 1024 < B.
+# B is laid out for a K10L grid of 256 workgroups (the compute units of an MI355X): 129 groups of eight samples (every workgroup one
+# group), 257 (workgroup 0 a second), 513 (a third: the first whose indices were requested two groups ahead), 769 (a fourth), with
+# every residue of B mod 8 in the last group.  (D, A) as above: the compiled shapes, and the generic forms at the ends of their
+# ranges -- 24-wide at D = 1, 7, 24; rolled 40-wide at D = 25, 40; A = 1, 2, 3, 8, 15, which cut layer 2 into 4, 4, 4, 3, 2 parts.
+LARGE_COMPILED = [(1025, 23, 9), (1031, 18, 9), (2049, 39, 9), (2056, 23, 9), (4097, 23, 9), (4104, 39, 9), (6151, 18, 9)]
+LARGE_GENERIC = [(1025, 1, 1), (1026, 1, 15), (2049, 24, 15), (2054, 25, 2), (4097, 40, 15), (1029, 40, 1), (4099, 7, 3), (2052, 24, 8)]
+LARGE_SHAPES = LARGE_COMPILED + LARGE_GENERIC
+LARGE_SATURATED = [(1025, 23, 9), (2049, 39, 9), (4097, 40, 15), (2054, 25, 2)]       # at scale 4000
+LARGE_APPLIED = [(2049, 39, 9), (4097, 23, 9), (2054, 25, 2), (1026, 1, 15)]          # four applied steps, max_norm 0.05 and 1e9
+LARGE_ROBUST = [(2049, 39, 9), (6151, 18, 9), (4097, 40, 15)]
+LARGE_CONST_ADV = [(2056, 23, 9), (4097, 23, 9)]                                      # every advantage 0.5
+LARGE_MAX_NORM, LARGE_IDLE_NORM = 0.05, 1e9      # tests/test_large_minibatch_gpu.py's: at these B the gradient norms are below 0.5
+WALK_SAMPLE = 8 * 256                            # the first sample of workgroup 0's second group on 256 compute units
+# (shape, scale, steps, max_norm) of every case tests/test_large_minibatch_f64_gpu.py runs against float64;
+# tests/test_large_minibatch_f64_host.py holds each to the input conditions
+LARGE_ONE_STEP = ([(s, scale, 1, LARGE_MAX_NORM) for scale in (1.0, 40.0) for s in LARGE_SHAPES]
+                  + [(s, 4000.0, 1, LARGE_MAX_NORM) for s in LARGE_SATURATED])
+LARGE_MULTI = [(s, 1.0, 4, mn) for s in LARGE_APPLIED for mn in (LARGE_MAX_NORM, LARGE_IDLE_NORM)]
 
 
 def n_param(D, A):
@@ -206,12 +238,38 @@ def wrong_gradients(c):
     return gradient_of(c, weight=w), gradient_of(c, flip=j)
 
 
-class Call:
-    """One pc_bc_minibatch / pc_ppo_minibatch (plain, prepared, diagnostics, epoch) call's device state.  grad is pre-filled with 7.0;
-    the workspace has pc_ppo_workspace_floats floats (the diagnostics forms: pc_ppo_diag_workspace_floats) and is pre-filled with
-    ws_fill.  shift = n > 0: grad, the moments, step, lr and metrics each start n floats into a larger allocation."""
+def walk_wrong_gradient(c):
+    """The wrong answer of the large step's walk (B > 2048): sample 8 * 256 dropped, the first sample of workgroup 0's second group --
+    what a workgroup would lose whose second group's rows never arrived."""
+    assert c["B"] > WALK_SAMPLE
+    w = np.ones(c["B"])
+    w[WALK_SAMPLE] = 0.0
+    return gradient_of(c, weight=w)
 
-    def __init__(self, param, B, D, A, max_norm=MAX_NORM, ec=EC, ws_fill=0.0, shift=0, diag=False):
+
+def adv_stats(idx2d, B, adv, idx_ld=None):
+    """pc_ppo_adv_stats on the index rows idx2d [n_mb][>= B] (device; row m starts idx_ld = idx2d.stride(0) elements after row m - 1
+    and its first B entries count) -> [n_mb][2] float32 (device).  Result and workspace are pre-filled with NaN."""
+    n_mb = idx2d.shape[0]
+    idx_ld = idx2d.stride(0) if idx_ld is None else idx_ld
+    assert idx2d.stride(1) == 1 and idx_ld >= B
+    stats = torch.full((n_mb, 2), float("nan"), device="cuda")
+    n_ws = lib.pc_ppo_adv_stats_workspace_doubles(n_mb, B)
+    assert n_ws > 0
+    ws = torch.full((n_ws,), float("nan"), device="cuda", dtype=torch.float64)
+    _capi.check(lib.pc_ppo_adv_stats(0, idx2d.data_ptr(), idx_ld, n_mb, B, adv.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream), "pc_ppo_adv_stats")
+    torch.cuda.synchronize()
+    return stats
+
+
+class Call:
+    """One pc_bc_minibatch / pc_ppo_minibatch (plain, prepared, diagnostics, epoch) / pc_ppo_minibatch_large call's device state.  grad
+    is pre-filled with 7.0; the workspace has pc_ppo_workspace_floats floats (the diagnostics forms: pc_ppo_diag_workspace_floats;
+    large = True: pc_ppo_large_workspace_floats on device 0) and is pre-filled with ws_fill.  shift = n > 0: grad, the moments, step,
+    lr and metrics each start n floats into a larger allocation."""
+
+    def __init__(self, param, B, D, A, max_norm=MAX_NORM, ec=EC, ws_fill=0.0, shift=0, diag=False, large=False):
         n = param.numel()
         assert n == n_param(D, A)
         self.B, self.D, self.A, self.max_norm, self.ec = B, D, A, max_norm, ec
@@ -228,7 +286,11 @@ class Call:
         self.step = buf(1, 0.0)
         self.lr = buf(1, LR)
         self.metrics = buf(4, 0.0)
-        n_ws = (lib.pc_ppo_diag_workspace_floats if diag else lib.pc_ppo_workspace_floats)(B, D, 256, A)
+        assert not (diag and large)
+        if large:
+            n_ws = lib.pc_ppo_large_workspace_floats(0, B, D, 256, A)
+        else:
+            n_ws = (lib.pc_ppo_diag_workspace_floats if diag else lib.pc_ppo_workspace_floats)(B, D, 256, A)
         assert n_ws > 0
         self.ws = torch.full((n_ws,), ws_fill, device="cuda")
         self.diag = torch.zeros(8, device="cuda") if diag else None
@@ -254,6 +316,13 @@ class Call:
         return self._done(lib.pc_ppo_minibatch(0, idx.data_ptr(), self.B, self.D, 256, self.A, obs.data_ptr(), act.data_ptr(), old_lp.data_ptr(),
                                                adv.data_ptr(), ret.data_ptr(), *self._state(), *self._coef(), self.metrics.data_ptr(),
                                                self.ws.data_ptr(), apply, torch.cuda.current_stream().cuda_stream), "pc_ppo_minibatch")
+
+    def large(self, idx, obs, act, old_lp, adv, ret, stats, apply=0):
+        """`stats`: this minibatch's (mean, std) pair from adv_stats (device)"""
+        return self._done(lib.pc_ppo_minibatch_large(0, idx.data_ptr(), self.B, self.D, 256, self.A, obs.data_ptr(), act.data_ptr(),
+                                                     old_lp.data_ptr(), adv.data_ptr(), ret.data_ptr(), stats.data_ptr(), *self._state(),
+                                                     *self._coef(), self.metrics.data_ptr(), self.ws.data_ptr(), apply,
+                                                     torch.cuda.current_stream().cuda_stream), "pc_ppo_minibatch_large")
 
     def ppo_diag(self, idx, obs, act, old_lp, adv, ret, apply=0, target_kl=0.0):
         return self._done(lib.pc_ppo_minibatch_diag(0, idx.data_ptr(), self.B, self.D, 256, self.A, obs.data_ptr(), act.data_ptr(),
