@@ -81,7 +81,12 @@ __global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict_
     const float invB = 1.0f / (float)B;
     const float a_raw = on ? adv[i] : 0.0f;
     const float mean = block_sum(a_raw, sh) * invB;
-    const float dev = on ? a_raw - mean : 0.0f;
+    // A float32 mean of advantages around 3 is good to an ulp of 3 (2.4e-7): 1e-4 of the deviation of a sample 0.003 from it, and dlogits
+    // carries that sample's deviation alone.  The deviations are therefore re-centred by their own mean (a - mean is exact near the
+    // mean, and their sum is small), which leaves each good to float32's relative precision.  Constant advantages: every term stays 0.
+    const float dev0 = on ? a_raw - mean : 0.0f;
+    const float recentre = block_sum(dev0, sh) * invB;
+    const float dev = on ? dev0 - recentre : 0.0f;
     const float var = block_sum(dev * dev, sh) / (float)(B - 1);   // unbiased, as Tensor.std() (train.py:239)
     const float sd = fmaxf(sqrtf(var), 1e-5f);                     // torch.max(std, 1e-5) (train.py:239-240)
     float pl = 0.0f, vl = 0.0f, ent = 0.0f, kl = 0.0f, clipped = 0.0f;   // (kl, clipped: DIAG only)
@@ -96,20 +101,27 @@ __global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict_
         float sum = 0.0f;
 #pragma unroll
         for (int k = 0; k < AMAX; ++k) sum += k < A ? expf(l[k] - mx) : 0.0f;
-        const float lse = mx + logf(sum);
+        const float lsum = logf(sum);
+        const float lse = mx + lsum;
         const int a = (int)act[i];
-        float new_lp = 0.0f;
+        float la = mx;
         float pk[AMAX], lpk[AMAX];
 #pragma unroll
         for (int k = 0; k < AMAX; ++k) {
             lpk[k] = k < A ? l[k] - lse : 0.0f;
             pk[k] = k < A ? expf(lpk[k]) : 0.0f;
             ent -= pk[k] * lpk[k];
-            if (k == a) new_lp = lpk[k];
+            if (k == a) la = l[k];
         }
-        const float r = expf(new_lp - old_lp[i]);                                  // :235
+        // logratio = (l_a - mx - log(sum)) - old_lp.  With logits of tens, l_a - lse is good to an ulp of the largest logit only (4e-6 at 60),
+        // and the ratio with it, while the log-ratio itself is a few tenths: l_a - mx is taken with its rounding error (TwoSum; no
+        // contraction, no reassociation in this unit), the two large terms d and old_lp cancel exactly, the small ones follow.
+        const float d = la - mx, z = d - la;
+        const float d_err = (la - (d - z)) + (-mx - z);
+        const float logratio = (d - old_lp[i]) + (d_err - lsum);
+        const float r = expf(logratio);                                            // :235
         if constexpr (DIAG) {
-            kl = (r - 1.0f) - (new_lp - old_lp[i]);
+            kl = (r - 1.0f) - logratio;
             clipped = fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
         }
         const float An = dev / sd;                                                 // :238-240

@@ -1712,6 +1712,7 @@ int pc_ppo_gather(int device, const int64_t* idx, int B, int D, const float* obs
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!idx || !obs || !act || !logprob || !adv || !ret || !o_obs || !o_act || !o_logprob || !o_adv || !o_ret || B < 1 || D < 1)
         return PC_ERR_INVALID_ARG;
+    if (device < 0) return PC_ERR_NO_DEVICE;      // (a machine without a device has no current one to tell -1 from: DeviceGuard would pass it)
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int total = B * (D + 4);
@@ -1730,6 +1731,7 @@ int pc_ppo_loss(int device, const float* logits, const float* values, const floa
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!logits || !values || !act || !old_logprob || !adv || !ret || !dlogits || !dvalues || !metrics) return PC_ERR_INVALID_ARG;
     if (B < 2 || B > 1024 || A < 1 || A > 16) return PC_ERR_UNSUPPORTED;
+    if (device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     const int threads = ((B + 63) / 64) * 64;
@@ -1743,6 +1745,7 @@ int pc_clip_adam(int device, float* param, float* grad, float* exp_avg, float* e
                  int64_t n, double max_norm, double grad_scale, double beta1, double beta2, double eps, void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr_dev || n < 1 || n > (1 << 26)) return PC_ERR_INVALID_ARG;
+    if (device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, step_count,
@@ -1811,6 +1814,7 @@ int pc_clip_adam_advanced(int device, float* param, const float* grad, float* ex
                           void* stream) {
     g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr_dev || n < 1 || n > (1 << 26)) return PC_ERR_INVALID_ARG;
+    if (device < 0) return PC_ERR_NO_DEVICE;
     DeviceGuard guard(device);
     if (!guard.ok) return PC_ERR_NO_DEVICE;
     hipLaunchKernelGGL(clip_adam_mb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, const_cast<float*>(grad),

@@ -40,6 +40,8 @@ SEEDS = {(2, 23, 9): 2,         # 1002: no sample outside the clip range, and to
          (256, 23, 9): 19,      # 1256: gradient norms of 0.39 .. 0.41, the norm clip at 0.5 never acts
          (1023, 40, 15): 1,     # 2023: norms of 0.24 .. 0.38
          (65, 25, 2): 2,        # 1065: a norm of 0.495 at the third step
+         (1024, 40, 16): 4,     # 2024: a norm of 0.37 at the fourth step (seeds 1, 3: norms of 0.22 .. 0.45; seed 2: a ratio 1.5e-6 from an
+                                #       edge in the idle-clip steps).  A = 16: tests/test_update_tail_f64_gpu.py, the learner's fused path
          # the large cases (conditions of tests/test_large_minibatch_f64_host.py)
          (2049, 39, 9): 2,      # 3049: at scale 4000 an inverted clip decision is 13 x the allowance; a ratio 8.2e-6 from an edge in the
                                 #       four idle-clip steps (seed 1: a flip that moves nothing at scale 4000)
