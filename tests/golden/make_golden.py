@@ -19,6 +19,7 @@ reward_scaling) are restated in `run_group` below from the gymnasium 0.29.1 beha
 
 Run:  python tests/golden/make_golden.py          (≈ 3 min, writes tests/golden/*.npz)
       python tests/golden/make_golden.py ppo      (seconds: tests/golden/ppo_minibatch.npz only -- lib/model.py's Agent)
+      python tests/golden/make_golden.py rays     (≈ 1 min: tests/golden/rays_<track>_n<n>.npz, the seven off-menu ray counts of tests/ray_counts_reference.py)
 """
 import os
 import sys
@@ -322,10 +323,45 @@ def ppo_cases():
     return out
 
 
+# `make_golden.py rays`: the off-menu ray counts of tests/ray_counts_reference.py.  Six policies each: a chase driver (gates), random
+# actions, constant forward (crashes through ray 0) and the three reversing actions 1, 6, 7 (crashes through the rear rays: at n = 90 and
+# n = 181 those have indices past 64).  (steps, seed, chase noise, chase speed) per count: fewer steps where an observation row is long,
+# so that no file outgrows tests/golden/env_track_n12.npz; seeds and drivers chosen so that tests/test_ray_counts_host.py's coverage
+# conditions hold (crashes, gates, at n = 7 a row where only ray 7 reads below 10 px, at n = 181 crashes through rays 135 / 180 alone).
+RAYS_RUNS = {4: (150, 3, 0.05, 6.0), 5: (150, 3, 0.05, 6.0), 7: (150, 1401, 0.05, 6.0), 11: (150, 3, 0.05, 6.0), 31: (150, 3, 0.05, 6.0),
+             90: (150, 3, 0.05, 6.0), 181: (70, 3, 0.05, 8.0)}
+
+
+def rays_cases(only=()):
+    sys.path.insert(0, os.path.dirname(OUT))
+    from ray_counts_reference import CASES
+    for track, n in CASES:
+        if only and str(n) not in only:
+            continue
+        T, seed, eps, vtarget = RAYS_RUNS[n]
+        env = make_env(track, n)
+        out = {"reset_obs": env._get_obs(), "reset_state": np.array(get_state(env)[:5], np.float64),
+               "walls": np.array([np.concatenate(b.get_points()) for b in env._CarEnv__boundaries], np.float64),
+               "gates": np.array([np.concatenate(g.get_points()) for g in env._CarEnv__reward_gates], np.float64),
+               "num_rays_nominal": np.int64(n), "reward_scaling": np.float64(REWARD_SCALING)}
+        policies = [("chase", eps, vtarget), ("random",), ("const", 0), ("const", 1), ("const", 6), ("const", 7)]
+        rec = run_group(track, n, policies, T, seed=seed)
+        del rec["ret_obs"]      # the reset observation where the step ended the episode, step_obs elsewhere: the loader rebuilds it
+        out.update(rec)
+        path = f"{OUT}/rays_{track}_n{n}.npz"
+        np.savez_compressed(path, **out)
+        gates = int((rec["post_passed"] > rec["pre_passed"]).sum())
+        print(f"{track} n={n}: D={len(out['reset_obs'])} steps {T} crashes {int(rec['terminated'].sum())} (per policy "
+              f"{rec['terminated'].sum(0).tolist()}) gates {gates} -> {os.path.getsize(path)} bytes", flush=True)
+
+
 def main():
     os.chdir(REF)  # the reference loads "lib/assets/car.png" relative to cwd (stubbed, but keep the cwd it expects)
     if sys.argv[1:] == ["ppo"]:               # `make_golden.py ppo`: only the PPO-minibatch fixture (reads the env fixtures for its observations)
         np.savez_compressed(f"{OUT}/ppo_minibatch.npz", **ppo_cases())
+        return
+    if sys.argv[1:2] == ["rays"]:             # `make_golden.py rays [n ...]`: the off-menu ray counts (all seven, or the listed ones)
+        rays_cases(sys.argv[2:])
         return
     if not sys.argv[1:]:
         np.savez_compressed(f"{OUT}/ray_cases.npz", **ray_unit_cases())

@@ -19,6 +19,7 @@ from conftest import TRACKS
 from oracle.scenarios import load_trained_policy
 from test_env_gpu import MARGIN_PX, OBS_TOL_F32
 import observe_reference as R
+import ray_counts_reference as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -239,3 +240,78 @@ def test_training_bits_with_and_without_landscape(tmp_path):
     assert models[0].keys() == models[1].keys()
     for k in models[0]:
         assert torch.equal(models[0][k].view(torch.int32), models[1][k].view(torch.int32)), k
+
+
+# ---- 9. the off-menu ray counts (tests/ray_counts_reference.py): the harvested oracle states in the golden rows' place ---------------------
+OFF_MENU = [(rc.TRACK_OF[n], n) for n in (5, 7, 11, 90, 181)]
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_against_the_reference(track, n, dtype):
+    """The poses the harvested steps end at, with the oracle's observation of them and whether they crashed: F64 handles give the
+    reference's bits, F32 handles stay within test_env_gpu.py's bars.  At 181 nominal rays the first rows are the recorded crashes of a
+    reversing car, which only rays 135 / 180 -- past the 64-bit collision mask -- see."""
+    g = rc.harvest(track, n)
+    turns = np.rint((g["post_rot"] - g["reset_state"][4]) / 5.0).astype(np.int32)
+    env = pc.VecCarEnv(1, TRACKS[track], num_rays=n, dtype=dtype)
+    obs, col = _observe(env, g["post_px"], g["post_py"], turns, g["post_vx"], g["post_vy"])
+    assert obs.shape == g["step_obs"].shape == (len(turns), 6 + rc.geometry(n)[1]) and set(np.unique(col)) <= {0, 1}
+    assert g["terminated"].sum() >= 100 and (~g["terminated"]).sum() >= 100
+    if dtype == "f64":
+        assert np.array_equal(_bits(obs), _bits(g["step_obs"]))
+        assert np.array_equal(col != 0, g["terminated"])
+    else:
+        _check_f32(obs, col, g["step_obs"], g["terminated"], g["wall_margin"] > MARGIN_PX)
+        assert (g["wall_margin"] > MARGIN_PX).mean() > 0.99
+    if n == 181:
+        k = g["n_high_ray_only"]
+        assert k >= 5 and rc.high_ray_only_crashes(g, track, n)[:k].all() and (g["wall_margin"][:k] > MARGIN_PX).all()
+        assert (col[:k] == 1).all()
+    env.close()
+
+
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_f32_observe_equals_step_bits(track, n):
+    N, T = 300, 40
+    env = pc.VecCarEnv(N, TRACKS[track], num_rays=n, reward_scaling=0.1, dtype="f32")
+    env.reset()
+    rng = np.random.default_rng(11)
+    actions = rng.integers(0, 9, size=(T, N))
+    actions[rng.random((T, N)) < 0.4] = 0
+    resets = 0
+    for t in range(T):
+        obs, rew, term, trunc, _ = env.step(torch.from_numpy(actions[t]).cuda())
+        seen = env.observe()
+        assert torch.equal(obs.view(torch.int32), seen.view(torch.int32)), t
+        resets += int(term.sum())
+    assert resets > 0 and env.last_step_kernel() == "K1"
+    env.close()
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("track,n", [(rc.TRACK_OF[n], n) for n in (90, 181)])
+def test_off_menu_ray_counts_observe_current_state(track, n, dtype):
+    """pc_env_observe on the handle's own state, set to the poses the harvested steps end at: F64 handles give the reference's bits,
+    F32 handles stay within the float32 bars; both the bits of observe_poses of the same poses, and the state is left alone."""
+    g = rc.harvest(track, n)
+    M = len(g["action"])
+    turns = np.rint((g["post_rot"] - g["reset_state"][4]) / 5.0).astype(np.int32)
+    env = pc.VecCarEnv(M, TRACKS[track], num_rays=n, dtype=dtype)
+    env.reset()
+    env.set_state(px=g["post_px"], py=g["post_py"], vx=g["post_vx"], vy=g["post_vy"], rot=g["post_rot"], time_step=np.arange(M) % 900 + 1)
+    before = env.get_state()
+    col = torch.full((M,), 7, dtype=torch.uint8, device="cuda")
+    obs = env.observe(collides=col).cpu().numpy()
+    col = col.cpu().numpy()
+    after = env.get_state()
+    for k in before:
+        assert np.array_equal(before[k].view(np.uint64) if before[k].dtype == np.float64 else before[k],
+                              after[k].view(np.uint64) if after[k].dtype == np.float64 else after[k]), k
+    obs_p, col_p = _observe(env, g["post_px"], g["post_py"], turns, g["post_vx"], g["post_vy"])
+    assert np.array_equal(_bits(obs), _bits(obs_p)) and np.array_equal(col, col_p)
+    if dtype == "f64":
+        assert np.array_equal(_bits(obs), _bits(g["step_obs"])) and np.array_equal(col != 0, g["terminated"])
+    else:
+        _check_f32(obs, col, g["step_obs"], g["terminated"], g["wall_margin"] > MARGIN_PX)
+    env.close()

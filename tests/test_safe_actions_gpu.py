@@ -16,6 +16,7 @@ from first_episode_reference import first_episodes_ref
 from oracle.scenarios import load_trained_policy
 import step_poses_reference as R
 import safe_actions_reference as S
+import ray_counts_reference as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -113,6 +114,37 @@ def test_f32_equals_chained_step_poses(track, n, recipe):
         M = len(s["px"])
         for m in want:
             assert all(c >= need * M for c, need in zip(S.classes(m), S.SHARES)), S.classes(m)
+    env.close()
+
+
+# ---- 2b. the off-menu ray counts (tests/ray_counts_reference.py): 7 collision rays of 8 rays; collision rays past the 64-bit mask ------------
+OFF_MENU = [(rc.TRACK_OF[n], n) for n in (7, 181)]
+
+
+@pytest.mark.parametrize("recipe", RECIPES)
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_f64_equals_the_reference(track, n, recipe):
+    s, ref = S.reference(track, n, recipe, 2)
+    env = _env(track, n, "f64")
+    for d in (1, 2):
+        _exact(_masks(env, s, d), ref[d - 1], (recipe, d))
+    if recipe == "pre_crash":      # empty, mixed and full masks at both depths
+        for m in ref[:2]:
+            assert all(c >= need * len(s["px"]) for c, need in zip(S.classes(m), S.SHARES)), S.classes(m)
+    env.close()
+
+
+@pytest.mark.parametrize("recipe", RECIPES)
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_f32_equals_chained_step_poses(track, n, recipe):
+    s = S.RECIPES[recipe](track, n)
+    env = _env(track, n, "f32")
+    want = _chained(env, s, 2)
+    for d in (1, 2):
+        _exact(_masks(env, s, d), want[d - 1], (recipe, d))
+    if recipe == "pre_crash":
+        for m in want:
+            assert all(c >= need * len(s["px"]) for c, need in zip(S.classes(m), S.SHARES)), S.classes(m)
     env.close()
 
 

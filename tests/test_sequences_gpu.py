@@ -17,6 +17,7 @@ from first_episode_reference import first_episodes_ref
 import oracle
 import step_poses_reference as R
 import sequences_reference as Q
+import ray_counts_reference as rc
 from test_sequences_host import PLAN_H, PLAN_K, PLAN_ROUNDS, PLAN_SEED
 
 pytestmark = pytest.mark.gpu
@@ -77,9 +78,21 @@ def _score(env, s, table, keys=tuple(o[0] for o in OUT), track_id=None, active=N
 
 
 # ---- 1. F64 handles: the CPU oracle ----------------------------------------------------------------------------------------------------
+OFF_MENU = [(rc.TRACK_OF[n], n) for n in (11, 90)]      # tests/ray_counts_reference.py: six collision rays; collision rays past the 64-bit mask
+
+
 @pytest.mark.parametrize("K,H", [(64, 1), (64, 3), (64, 12), (70, 12), (1, 12)])
 @pytest.mark.parametrize("track,n", Q.CONFIGS)
 def test_f64_equals_the_reference(track, n, K, H):
+    _f64_equals_the_reference(track, n, K, H)
+
+
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_f64_equals_the_reference(track, n):
+    _f64_equals_the_reference(track, n, 70, 3)
+
+
+def _f64_equals_the_reference(track, n, K, H):
     env = _env(track, n, "f64")
     for recipe in Q.RECIPES:
         s, ref = Q.reference(track, n, recipe, H, K)
@@ -125,11 +138,19 @@ def _chained(env, s, table, track_id=None):
 
 @pytest.mark.parametrize("track,n", Q.CONFIGS)
 def test_f32_equals_chained_step_poses(track, n):
-    K, H = Q.K_REF, Q.H_REF
+    _f32_equals_chained_step_poses(track, n, Q.K_REF, Q.H_REF)
+
+
+@pytest.mark.parametrize("track,n", OFF_MENU)
+def test_off_menu_ray_counts_f32_equals_chained_step_poses(track, n):
+    _f32_equals_chained_step_poses(track, n, 70, 3)
+
+
+def _f32_equals_chained_step_poses(track, n, K, H):
     env, env64 = _env(track, n, "f32"), _env(track, n, "f64")
     left_out = pairs = 0
     for recipe in Q.RECIPES:
-        s, ref = Q.reference(track, n, recipe)
+        s, ref = Q.reference(track, n, recipe, H, K)
         got = _score(env, s, Q.table(H, K))
         _same(got, _chained(env, s, Q.table(H, K)), Q.OUT_KEYS + Q.BEST_KEYS, recipe)
         # status and steps are the F64 handle's wherever no collision ray of the F64 reference comes within 1e-6 px of the 10 px threshold
