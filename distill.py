@@ -45,6 +45,10 @@ def parse_args(argv=None):
     ap.add_argument("--plan-gamma", type=float, default=argparse.SUPPRESS, metavar="G", help="discount of a sequence's rewards, 0 .. 1 (default 1)")
     ap.add_argument("--plan-bootstrap", choices=("none", "running", "running_truncated"), default=argparse.SUPPRESS, help="add gamma^n * the critic's "
                     "value of the state a sequence ends in; needs --teacher-checkpoint (default none)")
+    ap.add_argument("--labels", choices=("best", "soft"), default="best", help="best: the first action of the teacher's best sequence; soft: a "
+                    "target over the actions from what the best sequence beginning with each one earned (exact ties share the mass)")
+    ap.add_argument("--label-temperature", type=float, default=0.0, metavar="T", help="--labels soft: softmax of the per-action returns / T, in "
+                    "units of the scaled return (0: all mass on the maximal actions)")
     ap.add_argument("--teacher-checkpoint", default=None, help="the agent whose critic the teacher bootstraps from (kept frozen)")
     ap.add_argument("--eval-every", type=int, default=0, metavar="R", help="evaluate the student after every R-th round (0 = never)")
     ap.add_argument("--eval-envs", type=int, default=1024)
@@ -56,6 +60,8 @@ def parse_args(argv=None):
         ap.error("--plan-bootstrap other than none needs --teacher-checkpoint: the critic that values the end states")
     if args.rounds < 1 or args.steps_per_round < 1 or args.epochs < 1:
         ap.error("--rounds, --steps-per-round and --epochs must be >= 1")
+    if not 0.0 <= args.label_temperature < float("inf") or (args.labels == "best" and args.label_temperature != 0.0):
+        ap.error("--label-temperature must be finite and >= 0, and needs --labels soft")
     if args.eval_every < 0 or args.eval_envs < 1:
         ap.error("--eval-every must be >= 0 and --eval-envs >= 1")
     return args
@@ -84,7 +90,7 @@ def main(argv=None):
     ds = pc.PlannerDistiller(agent, args.track, n_envs=args.envs, num_rays=args.num_rays, planner=planner, steps_per_round=args.steps_per_round,
                              beta0=args.beta0, beta_decay=args.beta_decay, epochs_per_round=args.epochs, aggregate=not args.no_aggregate,
                              learner=dict(learning_rate=args.learning_rate, batch_size=args.batch_size, ent_coef=args.ent_coef), seed=args.seed,
-                             rounds=args.rounds, reward_scaling=args.reward_scaling)
+                             rounds=args.rounds, reward_scaling=args.reward_scaling, labels=args.labels, label_temperature=args.label_temperature)
     ev = None
     lines = []
     try:

@@ -468,6 +468,36 @@ int pc_cem_sample(int device, const uint32_t* weights, int64_t M, int H, int K, 
 int pc_cem_refit(int device, uint32_t* weights, const double* ret, const uint8_t* table, int64_t M, int H, int K, int E, int shift,
                  int w_min, const uint8_t* active, uint8_t* best_seq, void* stream);
 
+/* ---- per-action returns of a score table (opt-in; K28): what the best sequence BEGINNING WITH each of the nine actions earned, and a
+ * soft target over the actions.  The scoring launches report the row's best sequence and its first action only; this says how the other
+ * eight first actions fared, whether two of them tie, and by how much the best one wins.  No env handle: a device index and a stream, as
+ * pc_cem_refit.  All DEVICE.
+ *   ret      float64 [M][K]: pc_env_rollout_sequences[_value][_state]'s output
+ *   actions  the table those returns belong to; only its first time row is read: state m, sequence k is the byte at
+ *            actions[m * actions_state_stride + k] (stride 0: a shared table); a byte above 8 counts as 8, as it acts
+ *   steps    int32, status uint8 [M][K]: the same launch's outputs, both given or both NULL.  A sequence is DEAD AT ONCE iff status is
+ *            given, its status is PC_FIRST_TERMINATED and its steps is 1 (it crashes in its first step)
+ *   active   uint8 [M] or NULL = every row; NOTHING of a row with 0 is written
+ * Outputs, [M][9] each:
+ *   count    int32: the number of sequences whose first action is a
+ *   q        float64: the return of the first maximum among them, compared as float64 in k ascending order, with that return's bits;
+ *            -inf where count is 0
+ *   alive    uint8: 1 iff a sequence of a is not dead at once (without status: iff count > 0)
+ *   accumulate != 0 merges the row's previous outputs first: q is replaced only by a strictly greater return, count is added, alive
+ *   is or-ed (the cross-entropy planner's iterations score the same state: their tables pool).  The first call of a state passes 0.
+ *   target   float32 or NULL, from the merged row.  S = the alive actions, qmax = the maximum of q over S.  S empty: nine zeros.
+ *            temperature == 0: (float)(1.0 / n) on the n actions of S with q == qmax -- exact ties share the mass --, 0 elsewhere.
+ *            temperature > 0: e_a = exp((q_a - qmax) / temperature) in float64 for a in S, summed in ascending a;
+ *            target_a = (float)(e_a / sum); 0 outside S.
+ *   One wave per state (4 per workgroup), nine running maxima per lane, nine butterflies with ties to the lower k; no atomics, no LDS:
+ *   exact for every launch geometry, two calls give the same bits.
+ * Checked before any device call, in this order: NULL ret / actions / q / count / alive; exactly one of steps / status NULL; M < 1;
+ * K outside 1 .. PC_SEQ_MAX_CANDIDATES; a temperature that is not finite or is negative: PC_ERR_INVALID_ARG; then the device
+ * (PC_ERR_NO_DEVICE); M above 2^31 - 1: PC_ERR_UNSUPPORTED.  Does not synchronise. */
+int pc_sequences_action_values(int device, const double* ret, const uint8_t* actions, int64_t actions_state_stride,
+                               const int32_t* steps, const uint8_t* status, const uint8_t* active, int64_t M, int K, int accumulate,
+                               double temperature, double* q, int32_t* count, uint8_t* alive, float* target, void* stream);
+
 /* ---- batched evaluation (opt-in: the entry points above are untouched): the FIRST episode of every env and its lap times, and the
  * deterministic action.  What the reference's log_video answers with one fresh episode (train.py:23-50) and every PPO library with
  * evaluate_policy: N fresh episodes from the start line, one per env.
@@ -772,6 +802,18 @@ int pc_bc_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, 
                     const float* target, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count,
                     const float* lr_dev, double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps,
                     float* metrics, float* workspace, int apply, void* stream);
+
+/* pc_bc_minibatch against SOFT targets: soft [M][A] float32 row-major (pc_sequences_action_values' target can serve) in label's place,
+ * everything else as above.  With p = row i of soft, w_i = sum_k p_ik (float32, the 16-lane row's reduction tree) and
+ * labelled_i = (w_i > 0) -- an all-zero row, or one that holds a NaN, is "no label":
+ *     ce_i  = labelled_i ? -sum_k p_ik log_softmax(logits_i)[k] : 0      ent_i, vl_i and the loss as above
+ *     d loss / d logit_k = labelled_i ? -(p_ik - w_i softmax_k) / B + the entropy term : +0
+ * A one-hot row gives pc_bc_minibatch's bits for that label.  The third compile-time head of the shared forward / backward body; the
+ * compiled and the generic shapes; no deferred, prepared, diagnostics or large form. */
+int pc_bc_minibatch_soft(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* soft,
+                         const float* target, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count,
+                         const float* lr_dev, double vf_coef, double ent_coef, double max_norm, double beta1, double beta2, double eps,
+                         float* metrics, float* workspace, int apply, void* stream);
 
 /* The same step on a minibatch gathered beforehand. pc_ppo_prepare gathers n_mb minibatches in ONE launch: minibatch m
  * reads its B indices at idx[m * idx_ld ...] and writes, at prepared + m * pc_ppo_prepared_floats(B, D), the sample rows

@@ -112,6 +112,7 @@ _sig = {
     "pc_sample": (_i, [_i, _vp, _i64, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
     "pc_cem_sample": (_i, [_i, _vp, _i64, _i, _i, C.c_uint64, C.c_uint64, _i, _vp, _vp, _vp, _vp]),
     "pc_cem_refit": (_i, [_i, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "pc_sequences_action_values": (_i, [_i, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "pc_first_episodes": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _vp, _vp]),
     "pc_greedy": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "pc_track_maps": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
@@ -141,6 +142,7 @@ _sig = {
     "pc_ppo_epoch_prepared": (_i, [_i, _vp, _i, _i, _i, _i, _i] + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _vp, _vp]),
     "pc_ppo_minibatch": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 5 + [_vp] * 6 + [_d] * 7 + [_vp, _vp, _i, _vp]),
     "pc_bc_minibatch": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 3 + [_vp] * 6 + [_d] * 6 + [_vp, _vp, _i, _vp]),
+    "pc_bc_minibatch_soft": (_i, [_i, _vp, _i, _i, _i, _i] + [_vp] * 3 + [_vp] * 6 + [_d] * 6 + [_vp, _vp, _i, _vp]),
     "pc_ppo_large_workspace_floats":(_i64, [_i, _i, _i, _i, _i]),
     "pc_ppo_large_parts": (_i, [_i, _i]),
     "pc_ppo_adv_stats_workspace_doubles": (_i64, [_i, _i]),

@@ -332,8 +332,11 @@ __global__ __launch_bounds__(256) void ppo_prepare_kernel(const int64_t* __restr
 // `act` holds the labels (outside 0 .. A-1: no label, the actor's lanes and the sample's ce / ent are exactly 0), `ret` the critic's
 // targets (nullptr: no value term, the value lane is exactly +0), old_lp / adv are not read and no advantage statistics are reduced;
 // (ce, vl, ent) take (pl, vl, ent)'s places in the metric partial.  The value lane, the entropy and everything outside the loss
-// section are the same statements for both.
-constexpr int LOSS_PPO = 0, LOSS_BC = 1;
+// section are the same statements for both.  LOSS_BC_SOFT (pc_bc_minibatch_soft): LOSS_BC against a row of A probabilities -- `act`
+// holds soft [M][A]; lane k of a sample's 16-lane row fetches its own entry p_k with the gather (no load inside the loss section),
+// w = the row's sum, w > 0 = labelled (a NaN row is not); ce = -sum_k p_k lp_k and dk's hard (k == a) - pk becomes p_k - w pk.  A
+// one-hot row has w == 1 and one non-zero product, so it gives LOSS_BC's bits.
+constexpr int LOSS_PPO = 0, LOSS_BC = 1, LOSS_BC_SOFT = 2;
 template <int DMAX, int AC = 0, int DC = 0, bool DEFER = false, bool DIAG = false, int LOSS = LOSS_PPO>
 __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __restrict__ idx, const int B, const int D_rt, const int A_rt,
                                                 const float* __restrict__ obs, const float* __restrict__ act,
@@ -500,6 +503,11 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
     // ---- second-level loads (addresses came from idx)
     float a_loc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, a_sum = 0.0f;
     float pre_mean = 0.0f, pre_sd = 1.0f;
+    [[maybe_unused]] float p_soft = 0.0f;      // LOSS_BC_SOFT: entry (u & 15) of sample (u >> 4)'s target row, for the loss section's lane
+    if constexpr (LOSS == LOSS_BC_SOFT) {
+        const int b = s0 + (u >> 4), k = u & 15;
+        if (u < S * 16 && b < B && k < A) p_soft = act[idx[b] * A + k];
+    }
     if (prep) {
         const float* ps = prep + (size_t)B * D;                           // act | old_lp | adv | ret | (mean, std, -, -)
         pre_mean = ps[4 * B];
@@ -522,7 +530,8 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
         }
         if (u < S) {
             const bool lv = s0 + u < B;
-            sSmp[u][0] = lv ? act[my_src] : 0.0f;
+            if constexpr (LOSS == LOSS_BC_SOFT) sSmp[u][0] = 0.0f;      // (the targets are per lane: p_soft above)
+            else sSmp[u][0] = lv ? act[my_src] : 0.0f;
             if constexpr (LOSS == LOSS_PPO) {
                 sSmp[u][1] = lv ? old_lp[my_src] : 0.0f;
                 sSmp[u][2] = lv ? adv[my_src] : 0.0f;
@@ -671,6 +680,26 @@ __device__ __forceinline__ void ppo_fwdbwd_body(const int wg, const int64_t* __r
             const float g_lp = (pl1 >= pl2 ? -An : 0.0f) * r * invB;
             if (k < A) dk = g_lp * ((k == a ? 1.0f : 0.0f) - pk) + ec * invB * pk * (lpk + ent);
             else if (k == A) dk = vf * dv * invB;
+        } else if constexpr (LOSS == LOSS_BC_SOFT) {
+            // cross-entropy against the row p: pl = -sum_k p_k lp_k; a row whose sum is not above 0 (NaN too) is "no label"
+            float w = p_soft;
+            w += PC_ROW_ROR(w, 8);
+            w += PC_ROW_ROR(w, 4);
+            w += PC_ROW_ROR(w, 2);
+            w += PC_ROW_ROR(w, 1);
+            const bool labelled = w > 0.0f;
+            float plp = p_soft * lpk;
+            plp += PC_ROW_ROR(plp, 8);
+            plp += PC_ROW_ROR(plp, 4);
+            plp += PC_ROW_ROR(plp, 2);
+            plp += PC_ROW_ROR(plp, 1);
+            pl = labelled ? -plp : 0.0f;
+            if (!labelled) ent = 0.0f;
+            const float dv = ret ? __shfl(o, (u & 48) + A, 64) - sSmp[sidx][3] : 0.0f;
+            vl = 0.5f * dv * dv;
+            const float g_lp = labelled ? -invB : 0.0f;
+            if (k < A) dk = labelled ? g_lp * (p_soft - w * pk) + ec * invB * pk * (lpk + ent) : 0.0f;
+            else if (k == A) dk = ret ? vf * dv * invB : 0.0f;
         } else {
             // cross-entropy against the label: pl = -log_softmax[label]; a label outside 0 .. A-1 (NaN too) is "no label"
             const float lab = sSmp[sidx][0];
@@ -822,6 +851,17 @@ __global__ __launch_bounds__(256) void bc_fwdbwd_kernel(const int64_t* __restric
                                                         float* __restrict__ partial, float* __restrict__ metric_partial) {
     ppo_fwdbwd_body<DMAX, AC, DC, false, false, LOSS_BC>(blockIdx.x, idx, B, D, A, obs, label, nullptr, nullptr, target, param, 0.0f, vf, ec, partial,
                                                          metric_partial, nullptr, AdamDefer{});
+}
+
+// pc_bc_minibatch_soft: the same launch with the soft-target head (LOSS_BC_SOFT): soft [M][A] float32 in label's place.
+template <int DMAX, int AC = 0, int DC = 0>
+__global__ __launch_bounds__(256) void bc_soft_fwdbwd_kernel(const int64_t* __restrict__ idx, const int B, const int D, const int A,
+                                                             const float* __restrict__ obs, const float* __restrict__ soft,
+                                                             const float* __restrict__ target, const float* __restrict__ param,
+                                                             const float vf, const float ec,
+                                                             float* __restrict__ partial, float* __restrict__ metric_partial) {
+    ppo_fwdbwd_body<DMAX, AC, DC, false, false, LOSS_BC_SOFT>(blockIdx.x, idx, B, D, A, obs, soft, nullptr, nullptr, target, param, 0.0f, vf, ec,
+                                                              partial, metric_partial, nullptr, AdamDefer{});
 }
 
 // K11: flat_grad[i] = sum_p partial[p][i] (fixed order: deterministic); block-wise squared-norm partials for the clip;

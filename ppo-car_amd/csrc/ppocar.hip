@@ -84,6 +84,7 @@
 #include "kernels/sequences_value.hpp"
 #include "kernels/gae_sample.hpp"
 #include "kernels/cem.hpp"
+#include "kernels/action_values.hpp"
 #include "kernels/evaluation.hpp"
 #include "kernels/track_maps.hpp"
 #include "kernels/render.hpp"
@@ -1330,6 +1331,26 @@ int pc_cem_refit(int device, uint32_t* weights, const double* ret, const uint8_t
     return PC_OK;
 }
 
+// K28: per-first-action returns of a score table, and the soft target over the actions that outlive their first step
+int pc_sequences_action_values(int device, const double* ret, const uint8_t* actions, int64_t actions_state_stride, const int32_t* steps,
+                               const uint8_t* status, const uint8_t* active, int64_t M, int K, int accumulate, double temperature, double* q,
+                               int32_t* count, uint8_t* alive, float* target, void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!ret || !actions || !q || !count || !alive) return PC_ERR_INVALID_ARG;
+    if ((steps == nullptr) != (status == nullptr)) return PC_ERR_INVALID_ARG;
+    if (M < 1) return PC_ERR_INVALID_ARG;
+    if (K < 1 || K > PC_SEQ_MAX_CANDIDATES) return PC_ERR_INVALID_ARG;
+    if (!std::isfinite(temperature) || temperature < 0.0) return PC_ERR_INVALID_ARG;
+    if (!valid_device(device)) return PC_ERR_NO_DEVICE;
+    DeviceGuard guard(device);
+    if (!guard.ok) return PC_ERR_NO_DEVICE;
+    if (M > INT_MAX) return PC_ERR_UNSUPPORTED;      // one wave per state
+    const ActionValues p{ret, actions, actions_state_stride, steps, status, active, M, K, accumulate, temperature, q, count, alive, target};
+    hipLaunchKernelGGL(action_values_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    HIPCHK(hipGetLastError());
+    return PC_OK;
+}
+
 // the compute-unit count of a device, asked once per device (ids from 64 on: 256).  The one cache of the library: two threads that
 // race on an entry store the same value.
 // pc_render_*: W and H of a scale on the list, false otherwise
@@ -2161,6 +2182,7 @@ int64_t pc_ppo_diag_workspace_floats(int B, int D, int H, int A) {
 struct MbSamples {      // the rollout's tensors and this minibatch's indices, or (prep) a block ppo_prepare_kernel gathered
     const int64_t* idx; const float *obs, *act, *old_logprob, *adv, *ret, *prep;
     bool bc = false;        // the cross-entropy step (K27): act = the labels, ret = the critic's targets or nullptr, no old_logprob / adv
+    bool soft = false;      // with bc: act = soft targets [M][A] (pc_bc_minibatch_soft)
     bool complete() const { return bc ? idx && obs && act : prep || (idx && obs && act && old_logprob && adv && ret); }
 };
 struct MbState { float *param, *grad, *exp_avg, *exp_avg_sq, *step_count; const float* lr_dev; };
@@ -2194,6 +2216,11 @@ static void launch_fwdbwd(const MbPlan& pl, int B, int D, int A, const MbSamples
             hipLaunchKernelGGL(kernel, dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.old_logprob, in.adv, in.ret, param,
                                (float)c.clip_ratio, (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial, in.prep, extra...);
         };
+        if (in.bc && in.soft) {
+            hipLaunchKernelGGL((bc_soft_fwdbwd_kernel<DM, AC, DC>), dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.ret, param,
+                               (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial);
+            return;
+        }
         if (in.bc) {
             hipLaunchKernelGGL((bc_fwdbwd_kernel<DM, AC, DC>), dim3(pl.n_part), dim3(256), 0, st, in.idx, B, D, A, in.obs, in.act, in.ret, param,
                                (float)c.vf_coef, (float)c.ent_coef, pl.partial, pl.metric_partial);
@@ -2274,6 +2301,17 @@ int pc_bc_minibatch(int device, const int64_t* idx, int B, int D, int H, int A, 
     if (!target && vf_coef != 0.0) return PC_ERR_INVALID_ARG;      // (NaN too: a value term needs its targets)
     const double clip_ratio = 0.0;                                 // (the cross-entropy head has no clip)
     return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, label, nullptr, nullptr, target, nullptr, true})), stream);
+}
+
+// the same step against soft targets [M][A] (the LOSS_BC_SOFT head)
+int pc_bc_minibatch_soft(int device, const int64_t* idx, int B, int D, int H, int A, const float* obs, const float* soft, const float* target,
+                         float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* step_count, const float* lr_dev, double vf_coef,
+                         double ent_coef, double max_norm, double beta1, double beta2, double eps, float* metrics, float* workspace, int apply,
+                         void* stream) {
+    g_hip_err.clear();   // (pc_last_hip_error speaks of THIS call)
+    if (!target && vf_coef != 0.0) return PC_ERR_INVALID_ARG;      // (NaN too: a value term needs its targets)
+    const double clip_ratio = 0.0;                                 // (the cross-entropy head has no clip)
+    return ppo_minibatch_impl(device, B, D, H, A, PC_MB_STEP((MbSamples{idx, obs, soft, nullptr, nullptr, target, nullptr, true, true})), stream);
 }
 
 int64_t pc_ppo_prepared_floats(int B, int D) {

@@ -6,14 +6,19 @@ bc_loss is the supervised loss in torch ops -- the torch path and the tests' ref
     vl_i  = 0.5 (v_i - target_i)^2
     loss  = (sum ce_i + vf_coef * sum vl_i - ent_coef * sum ent_i) / B
 The divisor is always B; a label outside 0 .. A-1 is "no label" (the planners' doomed states carry -1).
+bc_soft_loss is the same loss against a row of probabilities p_i [A] (pc_sequences_action_values' target): w_i = sum_k p_ik,
+labelled_i = w_i > 0 (an all-zero or NaN row is "no label"), ce_i = -sum_k p_ik log_softmax(logits_i)[k]; a one-hot row gives bc_loss.
 
 BCLearner owns the flat parameter bucket and a device-side Adam, as PPOLearner does, and takes one minibatch per step(): on the
 GPU with the standard 256-wide agent pc_bc_minibatch (K27 + K11 + K12: no library GEMM, fixed summation order), otherwise bc_loss +
-autograd + clip_grad_norm_ + torch.optim.Adam(eps=1e-5).
+autograd + clip_grad_norm_ + torch.optim.Adam(eps=1e-5).  A 2-D label [M, A] is a table of soft targets: pc_bc_minibatch_soft /
+bc_soft_loss.
 
 PlannerDistiller runs DAgger on its own VecCarEnv: per round, `steps_per_round` steps from a reset in which the teacher (Planner /
 CEMPlanner on the env's exact model) labels every env's current state and env i executes the teacher's action if it belongs to the
-teacher's share of the round (teacher_envs), the student's sampled action otherwise; then BCLearner.fit on the labelled states."""
+teacher's share of the round (teacher_envs), the student's sampled action otherwise; then BCLearner.fit on the labelled states.
+labels="soft": the teacher also reports what the best sequence beginning with each action earned (K28) and the student is fitted to
+the soft row over the actions -- exact ties share the mass -- while the envs execute what they execute under labels="best"."""
 import math
 
 import numpy as np
@@ -38,6 +43,25 @@ def bc_loss(agent, obs, label, target, vf_coef, ent_coef):
     ce = -(logp.gather(1, a.view(-1, 1)).view(-1) * w).sum() / B
     safe = torch.clamp(logp, min=torch.finfo(logp.dtype).min)      # (Categorical.entropy's guard: 0 * -inf)
     ent = (-(safe.exp() * safe).sum(-1) * w).sum() / B
+    if target is None:
+        vl = torch.zeros((), dtype=logits.dtype, device=logits.device)
+    else:
+        vl = 0.5 * ((agent.critic(obs).view(-1) - target) ** 2).sum() / B
+    return ce + vf_coef * vl - ent_coef * ent, ce, vl, ent
+
+
+def bc_soft_loss(agent, obs, soft, target, vf_coef, ent_coef):
+    """(total, ce, vl, ent) of one minibatch against soft targets, any device and dtype.  soft [B, A]; target [B] or None (vl = 0)."""
+    logits = agent.actor(obs)
+    B, A = logits.shape
+    logp = F.log_softmax(logits, dim=-1)
+    w = soft.sum(-1)
+    labelled = w > 0      # (a NaN row fails the comparison)
+    on = labelled.to(logits.dtype)
+    safe = torch.clamp(logp, min=torch.finfo(logp.dtype).min)      # (Categorical.entropy's guard: 0 * -inf)
+    p = torch.where(labelled.view(-1, 1), soft, torch.zeros_like(soft))
+    ce = -(p * safe).sum(-1).sum() / B      # (row by row: a one-hot row's sum is log p of its action, bc_loss's term)
+    ent = (-(safe.exp() * safe).sum(-1) * on).sum() / B
     if target is None:
         vl = torch.zeros((), dtype=logits.dtype, device=logits.device)
     else:
@@ -100,26 +124,32 @@ class BCLearner:
             raise ValueError("BCLearner: vf_coef != 0 needs the critic's targets")
 
     def step(self, idx, obs, label, target=None):
-        """One minibatch: idx int64 [batch_size] into obs [M, D], label [M] float32 (act_buf's layout), target [M] float32 or None.
-        metrics += (ce, vl, ent, total); enqueues only."""
+        """One minibatch: idx int64 [batch_size] into obs [M, D], label [M] float32 (act_buf's layout) or [M, A] float32 (soft targets,
+        row-major), target [M] float32 or None.  metrics += (ce, vl, ent, total); enqueues only."""
         self._need_target(target)
         if idx.numel() != self.batch_size:
             raise ValueError(f"BCLearner.step: idx must hold batch_size = {self.batch_size} indices, got {idx.numel()}")
+        soft = label.dim() == 2
+        if label.dim() > 2 or (soft and label.shape[1] != self.agent.actor[2].out_features):
+            raise ValueError(f"BCLearner.step: label must be [M] or [M, {self.agent.actor[2].out_features}], not {tuple(label.shape)}")
         if self.path == "custom":
             for name, t in (("idx", idx), ("obs", obs), ("label", label), ("target", target)):
                 want = torch.int64 if name == "idx" else torch.float32
                 if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == want):
                     raise ValueError(f"BCLearner.step: {name} must be a contiguous {want} tensor on the device")
-            if obs.dim() != 2 or obs.shape[1] != self._dha[0] or label.numel() != obs.shape[0] or (target is not None and target.numel() != obs.shape[0]):
-                raise ValueError("BCLearner.step: obs must be [M, D] and label / target [M]")
+            if (obs.dim() != 2 or obs.shape[1] != self._dha[0] or label.numel() != obs.shape[0] * (self._dha[2] if soft else 1)
+                    or (target is not None and target.numel() != obs.shape[0])):
+                raise ValueError("BCLearner.step: obs must be [M, D], label [M] or [M, A] and target [M]")
             di = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            check(lib.pc_bc_minibatch(di, idx.data_ptr(), self.batch_size, *self._dha, obs.data_ptr(), label.data_ptr(),
-                                      target.data_ptr() if target is not None else None, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                                      self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(),
-                                      self.vf_coef, self.ent_coef, self.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
-                                      self._ws.data_ptr(), 1, torch.cuda.current_stream(self.device).cuda_stream), "pc_bc_minibatch")
+            step, name = (lib.pc_bc_minibatch_soft, "pc_bc_minibatch_soft") if soft else (lib.pc_bc_minibatch, "pc_bc_minibatch")
+            check(step(di, idx.data_ptr(), self.batch_size, *self._dha, obs.data_ptr(), label.data_ptr(),
+                       target.data_ptr() if target is not None else None, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
+                       self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.lr_dev.data_ptr(),
+                       self.vf_coef, self.ent_coef, self.max_grad_norm, 0.9, 0.999, 1e-5, self.metrics.data_ptr(),
+                       self._ws.data_ptr(), 1, torch.cuda.current_stream(self.device).cuda_stream), name)
         else:
-            loss, ce, vl, ent = bc_loss(self.agent, obs[idx], label[idx], None if target is None else target[idx], self.vf_coef, self.ent_coef)
+            loss, ce, vl, ent = (bc_soft_loss if soft else bc_loss)(self.agent, obs[idx], label[idx], None if target is None else target[idx],
+                                                                    self.vf_coef, self.ent_coef)
             self.flat_grad.zero_()
             loss.backward()
             nn.utils.clip_grad_norm_(self.agent.parameters(), self.max_grad_norm)
@@ -139,7 +169,7 @@ class BCLearner:
         return torch.from_numpy(host).to(self.device)
 
     def fit(self, obs, label, target=None, epochs=1):
-        """epochs x (M // batch_size) minibatch steps over obs [M, D] / label [M] (/ target [M]); the bc/* scalars as means over
+        """epochs x (M // batch_size) minibatch steps over obs [M, D] / label [M] or [M, A] (/ target [M]); the bc/* scalars as means over
         the steps taken.  One fetch, at the end."""
         self._need_target(target)
         idx = self.draw_indices(obs.shape[0], epochs)
@@ -183,12 +213,23 @@ class PlannerDistiller:
     teacher; seed defaults to this distiller's).  learner: BCLearner's keywords.  rounds: how many rounds' rows are allocated.
     reward_scaling is the env's, and so the scale of the returns the teacher compares: with a bootstrap it must be the one the
     teacher agent's critic was trained at (PPOConfig's default, 0.1).
+    labels: "best" -- the first action of the teacher's best sequence, a hard label -- or "soft": the teacher is built with
+    action_values=True, temperature=label_temperature, its soft row of every state goes to soft_buf [rounds, T, N, 9] beside label_buf
+    (filled as under "best") and train() fits on soft_buf.  The temperature is in units of the SCALED return (reward_scaling).
 
     Round r: the teacher's share is beta_r = beta0 * beta_decay^r of the envs (teacher_envs); step t of the round plans with
     step_index = r * steps_per_round + t and the student samples from the stream (agent.rng_seed, offset = step_index)."""
 
     def __init__(self, agent, tracks, n_envs=1024, num_rays=16, planner=None, steps_per_round=250, beta0=1.0, beta_decay=0.5,
-                 epochs_per_round=4, aggregate=True, learner=None, seed=0, device="cuda", dtype="f32", rounds=8, reward_scaling=0.1):
+                 epochs_per_round=4, aggregate=True, learner=None, seed=0, device="cuda", dtype="f32", rounds=8, reward_scaling=0.1,
+                 labels="best", label_temperature=0.0):
+        if labels not in ("best", "soft"):
+            raise ValueError(f"PlannerDistiller: labels must be 'best' or 'soft', not {labels!r}")
+        self.labels, self.label_temperature = labels, float(label_temperature)
+        if not (0.0 <= self.label_temperature < float("inf")):      # (NaN fails both comparisons)
+            raise ValueError(f"PlannerDistiller: label_temperature must be finite and >= 0, not {label_temperature!r}")
+        if labels == "best" and self.label_temperature != 0.0:
+            raise ValueError("PlannerDistiller: label_temperature needs labels='soft'")
         if int(steps_per_round) < 1 or int(rounds) < 1 or int(epochs_per_round) < 1:
             raise ValueError("PlannerDistiller: steps_per_round, rounds and epochs_per_round must be >= 1")
         if not 0.0 <= float(beta0) <= 1.0 or not 0.0 <= float(beta_decay) <= 1.0:
@@ -198,6 +239,8 @@ class PlannerDistiller:
         if self.kind not in ("shooting", "cem"):
             raise ValueError(f"PlannerDistiller: planner kind must be 'shooting' or 'cem', not {self.kind!r}")
         pk.setdefault("seed", seed)
+        if labels == "soft":
+            pk.update(action_values=True, temperature=self.label_temperature)
         lk = dict(learner if learner is not None else {})
         lk.setdefault("seed", seed)
         self.learner = BCLearner(agent, device=device, **lk)
@@ -220,6 +263,9 @@ class PlannerDistiller:
         self._student = torch.empty(N, dtype=torch.int64, device=dev)
         self._greedy = torch.empty(T * N, dtype=torch.int64, device=dev)
         self._no_label = torch.full((N,), -1, dtype=torch.int64, device=dev)
+        if labels == "soft":
+            self.soft_buf = torch.empty(self.rounds, T, N, self.envs.act_dim, dtype=torch.float32, device=dev)
+            self._soft_stats = torch.zeros(3, dtype=torch.float64, device=dev)      # the round's non-zero rows, tied rows, entropy sum
 
     def beta(self, r):
         return self.beta0 * self.beta_decay ** int(r)
@@ -240,6 +286,9 @@ class PlannerDistiller:
         self.envs.reset(out=obs)
         if cem:
             self.planner.reset_plan()
+        soft = self.labels == "soft"
+        if soft:
+            self._soft_stats.zero_()
         for t in range(T):
             step_index = r * T + t
             ta = self.planner.act(step_index, done=done) if cem else self.planner.act(step_index)
@@ -249,6 +298,14 @@ class PlannerDistiller:
             doomed = (out["status"].gather(1, bk).view(-1) == PC_FIRST_TERMINATED) & (out["steps"].gather(1, bk).view(-1) == 1)
             self.obs_buf[r, t].copy_(obs)
             self.label_buf[r, t].copy_(torch.where(doomed, self._no_label, ta))
+            if soft:
+                p = out["soft"]
+                self.soft_buf[r, t].copy_(p)
+                top = p.max(-1).values
+                some = top > 0
+                ent = -(p * torch.log(torch.where(p > 0, p, torch.ones_like(p)))).sum(-1)
+                self._soft_stats += torch.stack([some.sum(), (some & ((p == top.view(-1, 1)).sum(-1) >= 2)).sum(),
+                                                 ent.sum()]).to(torch.float64)
             action = ta
             if mixed:
                 self.agent.act(obs, out_action=self._student, offset=step_index, repack=t == 0)      # (the weights rest while collecting)
@@ -258,11 +315,19 @@ class PlannerDistiller:
 
     @torch.no_grad()
     def measure(self, r, chunk=65536):
-        """Device tensor [2]: (labelled states of round r whose label the student's greedy action equals, labelled states)."""
+        """Device tensor [2]: (labelled states of round r whose label the student's greedy action equals, labelled states).
+        labels="soft": a state is labelled where its soft row is non-zero, and the student agrees where its greedy action is one of
+        the row's maximal entries."""
         T, N, D = self.steps_per_round, self.envs.num_envs, self.envs.obs_dim
         obs, label = self.obs_buf[r].view(T * N, D), self.label_buf[r].view(T * N)
         for i in range(0, T * N, chunk):
             self.agent.act(obs[i:i + chunk], out_action=self._greedy[i:i + chunk], greedy=True, repack=i == 0)
+        if self.labels == "soft":
+            p = self.soft_buf[r].view(T * N, -1)
+            top = p.max(-1).values
+            labelled = top > 0
+            hit = p.gather(1, self._greedy.view(-1, 1)).view(-1) == top
+            return torch.stack([(hit & labelled).sum(), labelled.sum()]).to(torch.float64)
         labelled = (label >= 0) & (label < self.envs.act_dim)
         return torch.stack([((self._greedy.to(torch.float32) == label) & labelled).sum(), labelled.sum()]).to(torch.float64)
 
@@ -271,14 +336,24 @@ class PlannerDistiller:
         T, N, D = self.steps_per_round, self.envs.num_envs, self.envs.obs_dim
         lo = 0 if self.aggregate else int(r)
         rows = (int(r) + 1 - lo) * T * N
+        if self.labels == "soft":
+            return self.learner.fit(self.obs_buf[lo:int(r) + 1].view(rows, D), self.soft_buf[lo:int(r) + 1].view(rows, -1),
+                                    epochs=self.epochs_per_round)
         return self.learner.fit(self.obs_buf[lo:int(r) + 1].view(rows, D), self.label_buf[lo:int(r) + 1].view(rows), epochs=self.epochs_per_round)
 
     def round(self, r):
         """collect, measure, train -> the bc/* scalars, bc/agreement (the share of this round's labelled states where the student's
-        greedy action equals the label, measured BEFORE training on them; 0 when nothing is labelled), bc/beta, bc/labelled."""
+        greedy action equals the label, measured BEFORE training on them; 0 when nothing is labelled), bc/beta, bc/labelled.
+        labels="soft" adds bc/ties (the share of the round's non-zero soft rows in which two or more entries equal the row's maximum)
+        and bc/label_entropy (the mean entropy of those rows, nats)."""
         self.collect(r)
         stats = self.measure(r)
+        soft_stats = self._soft_stats.tolist() if self.labels == "soft" else None
         out = self.train(r)
+        if soft_stats is not None:
+            rows, tied, ent = soft_stats
+            out["bc/ties"] = tied / rows if rows > 0 else 0.0
+            out["bc/label_entropy"] = ent / rows if rows > 0 else 0.0
         agree, labelled = stats.tolist()
         out["bc/agreement"] = agree / labelled if labelled > 0 else 0.0
         out["bc/beta"] = self.beta(r)

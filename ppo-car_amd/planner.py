@@ -20,6 +20,12 @@ is scored by its discounted return plus gamma^n * the agent's critic at the stat
 fused policy step, K26), so a short horizon sees what a long one would; CEM then refits on those returns.  The agent's weights are packed
 once per act() / plan().  The defaults make the calls, and give the bits, the planners always did.
 
+Both planners take action_values=False, temperature=0.0: when on, pc_sequences_action_values (K28) follows every scoring launch and
+`out` gains q float64 [N, 9] (what the best sequence beginning with each action earned, -inf where none does), q_count int32, q_alive
+uint8 (an action with a sequence that survives its first step) and soft float32 [N, 9] (the target over the alive actions: exact
+ties share the mass at temperature 0, a softmax of q / temperature above it).  CEM pools its iterations' tables.  act() returns
+what it returns without; off, nothing is allocated or launched.
+
 PlannerEvaluator is the Evaluator's counterpart for the planner: the first episodes of N fresh envs, PC_TIME_LIMIT steps of act() +
 pc_env_step, pc_first_episodes over windows, reported through evaluation_scalars -- the same eval/* keys a policy evaluation prints, so
 a trained policy's lap and crash figures have something to stand beside."""
@@ -47,6 +53,29 @@ def _critic_args(who, envs, agent, gamma, bootstrap):
     return dict(gamma=gamma, bootstrap=bootstrap, agent=agent)
 
 
+def _action_value_args(who, action_values, temperature):
+    temperature = float(temperature)
+    if not (0.0 <= temperature < float("inf")):      # (NaN fails both comparisons)
+        raise ValueError(f"{who}: temperature must be finite and >= 0, not {temperature!r}")
+    return bool(action_values), temperature
+
+
+def _action_value_out(on, M, dev):
+    """the tensors K28 fills, for a planner's `out` dict"""
+    if not on:
+        return {}
+    return dict(q=torch.empty(M, N_ACTIONS, dtype=torch.float64, device=dev), q_count=torch.empty(M, N_ACTIONS, dtype=torch.int32, device=dev),
+                q_alive=torch.empty(M, N_ACTIONS, dtype=torch.uint8, device=dev), soft=torch.empty(M, N_ACTIONS, dtype=torch.float32, device=dev))
+
+
+def _action_values(dev, out, table, state_stride, M, K, active_ptr, accumulate, temperature):
+    """one K28 launch on the scoring launch's outputs in `out`"""
+    check(lib.pc_sequences_action_values(dev.index, out["ret"].data_ptr(), table.data_ptr(), state_stride, out["steps"].data_ptr(),
+                                         out["status"].data_ptr(), active_ptr, M, K, int(accumulate), temperature, out["q"].data_ptr(),
+                                         out["q_count"].data_ptr(), out["q_alive"].data_ptr(), out["soft"].data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream), "pc_sequences_action_values")
+
+
 def _critic_out(kw, envs, M, K):
     """the tensors the value form fills beside K22's, for a planner's `out` dict"""
     if not kw or kw["agent"] is None:
@@ -57,7 +86,9 @@ def _critic_out(kw, envs, M, K):
 
 
 class Planner:
-    def __init__(self, envs, horizon=16, candidates=256, seed=0, agent=None, gamma=1.0, bootstrap="none"):
+    def __init__(self, envs, horizon=16, candidates=256, seed=0, agent=None, gamma=1.0, bootstrap="none", action_values=False,
+                 temperature=0.0):
+        self.action_values, self.temperature = _action_value_args("Planner", action_values, temperature)
         if not 1 <= int(horizon) <= PC_TIME_LIMIT:
             raise ValueError(f"Planner: horizon must be 1 .. {PC_TIME_LIMIT}, not {horizon!r}")
         if not N_ACTIONS <= int(candidates) <= PC_SEQ_MAX_CANDIDATES:
@@ -76,6 +107,7 @@ class Planner:
                         status=torch.empty(N, K, dtype=torch.uint8, device=dev), best_k=torch.empty(N, dtype=torch.int32, device=dev),
                         best_action=torch.empty(N, dtype=torch.int64, device=dev), best_ret=torch.empty(N, dtype=torch.float64, device=dev))
         self.out.update(_critic_out(self._critic, envs, N, K))
+        self.out.update(_action_value_out(self.action_values, N, dev))
 
     def candidate_table(self, step_index):
         """The shared table of this step, uint8 [H, K] on the device (self.table, overwritten by every call)."""
@@ -90,6 +122,8 @@ class Planner:
         """int64 [N]: the first action of each env's best candidate from its current state (self.out["best_action"], overwritten by
         every call).  The env state is not modified; no host synchronisation."""
         self.envs.score_sequences(self.candidate_table(step_index), out=self.out, **self._critic)      # (an agent is packed here, once)
+        if self.action_values:
+            _action_values(self.device, self.out, self.table, 0, self.envs.num_envs, self.candidates, None, False, self.temperature)
         return self.out["best_action"]
 
     def drive(self, n_steps, start=0, out=None):
@@ -109,7 +143,8 @@ class CEMPlanner:
     STATE_KEYS = ("px", "py", "vx", "vy", "turns")      # of plan(states=...): required; next_gate, time_step, track_id, active optional
 
     def __init__(self, envs, horizon=16, candidates=64, elites=8, iterations=4, smoothing_shift=1, min_weight=64, init_weight=7281,
-                 warm_start=True, seed=0, agent=None, gamma=1.0, bootstrap="none"):
+                 warm_start=True, seed=0, agent=None, gamma=1.0, bootstrap="none", action_values=False, temperature=0.0):
+        self.action_values, self.temperature = _action_value_args("CEMPlanner", action_values, temperature)
         if not 1 <= int(horizon) <= PC_CEM_MAX_HORIZON:
             raise ValueError(f"CEMPlanner: horizon must be 1 .. {PC_CEM_MAX_HORIZON}, not {horizon!r}")
         if not N_ACTIONS + 1 <= int(candidates) <= PC_SEQ_MAX_CANDIDATES:
@@ -147,6 +182,7 @@ class CEMPlanner:
                         status=torch.empty(M, K, dtype=torch.uint8, device=dev), best_k=torch.empty(M, dtype=torch.int32, device=dev),
                         best_action=torch.empty(M, dtype=torch.int64, device=dev), best_ret=torch.empty(M, dtype=torch.float64, device=dev))
         self.out.update(_critic_out(self._critic, self.envs, M, K))
+        self.out.update(_action_value_out(self.action_values, M, dev))
 
     def reset_plan(self):
         """Every state's weights back to init_weight: the plan of a planner just made."""
@@ -196,6 +232,8 @@ class CEMPlanner:
                                             next_gate=states.get("next_gate"), time_step=states.get("time_step"),
                                             track_id=states.get("track_id"), active=active, out=self.out, **kw)
             self.iter_best_ret[i].copy_(self.out["best_ret"])
+            if self.action_values:      # the iterations score the same state: their tables pool
+                _action_values(dev, self.out, self.table, H * K, M, K, act_ptr, i > 0, self.temperature)
             check(lib.pc_cem_refit(dev.index, self.weights.data_ptr(), self.out["ret"].data_ptr(), self.table.data_ptr(), M, H, K,
                                    self.elites, self.smoothing_shift, self.min_weight, act_ptr, self.best_seq.data_ptr(), stream),
                   "pc_cem_refit")

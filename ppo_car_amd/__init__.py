@@ -18,4 +18,4 @@ from .track_maps import TrackMaps  # noqa: E402,F401
 from .landscape import PolicyLandscape  # noqa: E402,F401
 from .renderer import Renderer  # noqa: E402,F401
 from .planner import CEMPlanner, Planner, PlannerEvaluator  # noqa: E402,F401
-from .imitation import BCLearner, PlannerDistiller, bc_loss, teacher_envs  # noqa: E402,F401
+from .imitation import BCLearner, PlannerDistiller, bc_loss, bc_soft_loss, teacher_envs  # noqa: E402,F401
